@@ -2,6 +2,16 @@
 """bench.py -- rays/sec of the render hot path on MI355X (BASELINE.json metric).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--workload c1|c2|c3|c4|c5] [--precision bf16|fp32]
+                    [--full] [--dump-outputs DIR]
+
+A plain run sets up, warms up, times K steps and prints one JSON line: metric, value, unit, higher_is_better, dtype,
+ms_per_step (milliseconds per timed step), the configuration and the roofline of the timed launches.  Everything that
+takes runs of its own -- the sub-records and cpu_baseline below -- runs only with --full.
+--dump-outputs DIR writes what the last timed step returned to its caller as DIR/<name>.npy (float32): rgb_map,
+disp_map, acc_map and the extras (rgb0, disp0, acc0, z_std) at N = 1, the gathered rgb_map, disp_map, acc_map of the
+last frame at N > 1.  The disparity of a ray with no weight (acc 0: 0 / 0, NaN as in the reference) is written as 0
+(dump_outputs).  The inputs (weights, poses, the seeded perturb draws) are the same from run to run for the same
+arguments, so two builds can be compared output for output.
 
 One "step" = one call of Renderer.render(H, W, K, coarse, fine, chunk, c2w=pose, retraw=False)
 (reference render_utils.py:176-238: rays from the pose, batch assembly, the chunk loop, both field
@@ -12,7 +22,7 @@ the reference's own default and what SURVEY.md section 8d prescribes for through
 
 N = 1 (the default, what BENCH_rNN records): BASELINE.json configs[1], the configuration the metric
 is quoted on -- Lego half-res 400x400 = 160 000 rays, 64 coarse + 128 fine samples, 4096-ray chunks.
-The line also carries sub-records measured in the same process after the main timed region:
+With --full the line also carries sub-records measured in the same process after the main timed region:
   perturb0  the same workload with perturb=0 (the deterministic parity configuration)
   fp32      the same workload on the exact-fp32 kernel (rays/s, TFLOP/s against the 157.3 TFLOP/s fp32 MFMA peak)
   c5_n1     the multi-GPU workload (below) on this one GPU: the N=1 point of the scaling curve
@@ -22,7 +32,7 @@ A step is one 800x800 frame (640 000 rays, 64+128, chunk 32768) of a fixed list 
 camera circle (synth.circle_poses(200)); rank r renders flat pixel range r of every frame and the finished
 [rays, 5] rows are gathered to rank 0 -- the gather of frame k runs on a side stream under the render of
 frame k+1 (nerf_shared_amd.dist.OverlappedGather); all gathers are complete when the clock stops.
-Sub-record frames_round_robin: the same K frames dealt whole to the ranks (rank r renders frames
+Sub-record frames_round_robin (--full): the same K frames dealt whole to the ranks (rank r renders frames
 r, r+N, ...; no data-path collective, the frames stay where they were rendered).
 
 The JSON line also carries
@@ -31,7 +41,7 @@ The JSON line also carries
                   against the 2.5 PFLOP/s dense bf16 MFMA peak.  `traffic` (HBM bytes per launch from
                   rocprofv3 --pmc passes) is reported only from a profiles/ summary made from THIS build
                   of the kernels (csrc hash match), else null.
-  cpu_baseline -- the CPU oracle (torch-CPU restatement of the reference, "port") on this box's host cores:
+  cpu_baseline -- (--full) the CPU oracle (torch-CPU restatement of the reference, "port") on this box's host cores:
                   all cores granted to the process and 1 thread, on bounded samples (N = 1 only).  Its `check`
                   entry is the metric's "PSNR vs ref": the rays of the 4096-ray batch the CPU leg timed, rendered by the
                   bf16 / fp32_split / fp32 modes and compared with the CPU image (PSNR, max |d rgb|, max |d acc|)
@@ -256,7 +266,38 @@ def parse_args(argv=None):
     ap.add_argument("--no-subrecords", action="store_true")
     ap.add_argument("--perturb", type=float, default=1.0)
     ap.add_argument("--workload", default=None, choices=sorted(WORKLOADS))
+    ap.add_argument("--full", action="store_true",
+                    help="also the sub-records and cpu_baseline (each takes runs of its own); --no-subrecords and "
+                         "--no-cpu-baseline drop parts of it again")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned as DIR/<name>.npy (float32)")
     return ap.parse_args(argv)
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(outdir, arrays, n_rays):
+    """arrays: {name: device tensor of n_rays rays (leading dimensions)} -> outdir/<name>.npy in float32.  Above 64 MiB in
+    all, a fixed seeded sample of the rays is written instead: the same rows of every array, as [rows, channels], and
+    their flat ray indices in ray_index.npy.
+    The disparity of a ray that holds no weight (acc exactly 0) is 1 / max(1e-10, 0 / 0) = NaN, in the reference as here;
+    it is written as 0, a value disparity takes nowhere else (elsewhere it is at least 1 / far), so that the files compare
+    element for element.  Any other non-finite value is written as it is."""
+    import numpy as np
+    os.makedirs(outdir, exist_ok=True)
+    host = {k: v.detach().float().cpu().numpy() for k, v in arrays.items()}
+    for disp, acc in (("disp_map", "acc_map"), ("disp0", "acc0")):
+        if disp in host and acc in host:
+            host[disp] = np.where(np.isnan(host[disp]) & (host[acc] == 0), np.float32(0), host[disp])
+    total = sum(a.nbytes for a in host.values())
+    if total > DUMP_LIMIT_BYTES:
+        rows = n_rays * DUMP_LIMIT_BYTES // (total + 8 * n_rays)          # the index column counts too
+        keep = np.sort(np.random.default_rng(0).choice(n_rays, rows, replace=False))
+        host = {k: a.reshape(n_rays, -1)[keep] for k, a in host.items()}
+        host["ray_index"] = keep.astype(np.float64)
+    for k, a in host.items():
+        np.save(os.path.join(outdir, k + ".npy"), a)
 
 
 def spawn_ranks(args):
@@ -295,6 +336,8 @@ def main():
     args = parse_args()
     if args.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("--steps must be >= 1 and --warmup >= 0")
     # Under torch.distributed.run RANK/WORLD_SIZE are set and this process is one rank.  Started plainly with
     # --gpus N > 1 (how the driver records its command), or with NERF_AMD_FORCE_COLLECTIVE=1 at N = 1 (the RCCL
     # world-1 smoke of the C5 path), this process only launches the ranks -- before anything touches the GPU.
@@ -358,8 +401,9 @@ def main():
         _lib.lib.nerf_amd_profile_collect(launches, ms, pts)      # classes: 0 exact fp32, 1 bf16, 2 split precision
         return [(int(launches[c]), float(ms[c]), float(pts[c])) for c in range(3)]
 
-    def run(wk, perturb, steps, warmup, precision=None, mode="pixel_ranges", profile=False):
-        """Time `steps` steps of workload wk.  Returns (seconds [max over ranks], rays per step, profile)."""
+    def run(wk, perturb, steps, warmup, precision=None, mode="pixel_ranges", profile=False, outputs=None):
+        """Time `steps` steps of workload wk.  Returns (seconds [max over ranks], rays per step, profile).  A dict passed
+        as `outputs` receives what the last step returned to its caller ({} on ranks that receive nothing)."""
         for m in models:
             m.precision = precision or args.precision
         renderer = render_utils.Renderer(**renderer_cfg(wk, perturb))
@@ -368,13 +412,20 @@ def main():
         poses_t = [torch.from_numpy(p) for p in poses]
         fm = fine_model if wk["Ni"] > 0 else None
 
+        def on_frame(i, rgb, disp, acc):
+            if outputs is not None:
+                outputs.update(rgb_map=rgb, disp_map=disp, acc_map=acc)
+
         def frames(first, count):
             if world == 1 and not (wk.get("poses") and dist.is_initialized()):
                 for k in range(first, first + count):
-                    renderer.render(H, W, K, models[0], fm, chunk=chunk, c2w=poses_t[k % len(poses_t)], retraw=False)
+                    ret = renderer.render(H, W, K, models[0], fm, chunk=chunk, c2w=poses_t[k % len(poses_t)], retraw=False)
+                    if outputs is not None:
+                        outputs.update(rgb_map=ret[0], disp_map=ret[1], acc_map=ret[2], **ret[3])
+                    del ret
             elif mode == "pixel_ranges" or world == 1:
                 nd.render_poses_gathered(renderer, H, W, K, chunk, [poses_t[k % len(poses_t)] for k in range(first, first + count)],
-                                         models[0], fm, on_frame=lambda i, rgb, disp, acc: None)
+                                         models[0], fm, on_frame=on_frame)
             else:       # whole frames round-robin: rank r renders frames r, r + world, ...
                 for k in range(first + rank, first + count, world):
                     renderer.render(H, W, K, models[0], fm, chunk=chunk, c2w=poses_t[k % len(poses_t)], retraw=False)
@@ -412,7 +463,11 @@ def main():
             dist.all_reduce(t, op=dist.ReduceOp.MAX)
         return float(t.item()), H * W, prof
 
-    dt, rays_per_step, prof = run(w, args.perturb, args.steps, args.warmup, profile=True)
+    last = {} if args.dump_outputs else None
+    dt, rays_per_step, prof = run(w, args.perturb, args.steps, args.warmup, profile=True, outputs=last)
+    if last:                                     # rank 0 (the only rank a gathered frame reaches)
+        dump_outputs(args.dump_outputs, last, rays_per_step)
+        del last
     dist_info.update(nd.gather_stats())          # per-frame gathers issued inside the timed region, and by which path
     if getattr(run, "per_rank", None):
         pr = run.per_rank
@@ -422,7 +477,7 @@ def main():
     launches, kern_ms, kern_pts = prof[cls]
 
     sub = {}
-    if not args.no_subrecords:
+    if args.full and not args.no_subrecords:
         if world == 1 and key == "c2":
             d0, n0, _ = run(w, 0.0, max(2, args.steps // 4), 1)
             sub["perturb0"] = {"value": n0 * max(2, args.steps // 4) / d0, "unit": "rays/s",
@@ -510,7 +565,7 @@ def main():
                          "flop_per_point": FLOP_PER_POINT, "points": kern_pts, "rank": 0},
         }
         out.update(sub)
-        if world == 1 and not args.no_cpu_baseline and key in ("c1", "c2"):
+        if args.full and world == 1 and not args.no_cpu_baseline and key in ("c1", "c2"):
             cpu = cpu_baseline(torch, synth, w, full_c1=not args.no_subrecords)
             chk = cpu.pop("_check", None)
             if chk is not None:

@@ -54,7 +54,7 @@ def test_self_launched_rccl_world_of_one_runs_the_c5_gather():
 
 
 def test_self_launched_two_ranks_share_the_gpu_over_gloo():
-    p = run_bench({"NERF_AMD_DIST_BACKEND": "gloo"}, "--gpus", "2", "--steps", "4", "--warmup", "1", "--no-cpu-baseline")
+    p = run_bench({"NERF_AMD_DIST_BACKEND": "gloo"}, "--gpus", "2", "--steps", "4", "--warmup", "1", "--full", "--no-cpu-baseline")
     out = result_line(p)
     assert out["n_gpus"] == 2 and out["scaling"] == "strong"
     assert out["dist"]["backend"] == "gloo" and out["dist"]["rccl_world"] is None and len(out["dist"]["rank_devices"]) == 2
@@ -74,11 +74,11 @@ def test_more_rccl_ranks_than_gpus_is_refused_before_any_collective():
 
 
 def test_default_line_carries_the_roofline_the_cpu_baseline_and_a_meaningful_psnr_check():
-    """`python bench.py` as the driver runs it at N = 1 (short: 3 steps, no sub-records): one JSON line with the contract's
+    """`python bench.py --full` at N = 1 (short: 3 steps, no sub-records): one JSON line with the contract's
     keys, `roofline` and `cpu_baseline`; and `cpu_baseline.check` -- the metric's "PSNR vs ref" -- on weights whose field has
     content (an all-white view would score infinity whatever the kernels do): fp32-class modes above 50 dB against the CPU
     image, bf16 above 33 dB."""
-    p = run_bench({}, "--steps", "3", "--warmup", "1", "--no-subrecords")
+    p = run_bench({}, "--steps", "3", "--warmup", "1", "--full", "--no-subrecords")
     line = result_line(p)
     for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline",
               "dtype", "data", "config", "roofline", "cpu_baseline"):
@@ -92,6 +92,33 @@ def test_default_line_carries_the_roofline_the_cpu_baseline_and_a_meaningful_psn
     assert chk["rays"] == 4096 and chk["ref_rgb_variance"] > 1e-2, chk
     m = chk["modes"]
     assert m["fp32"]["psnr_db"] > 50 and m["fp32_split"]["psnr_db"] > 50 and m["bf16"]["psnr_db"] > 33, m
+
+
+def test_plain_line_is_lean_and_dumps_the_same_outputs_every_run(tmp_path):
+    """`python bench.py` without --full: the headline only (no sub-records, no cpu_baseline), `steps` timed steps; with
+    --dump-outputs the last step's maps land as finite float32 .npy files, equal bit for bit between two runs of the same
+    arguments (seeded perturb draws), and the right size for one 400x400 view.  (The timed workload's fine field is
+    empty: every ray's acc is 0 and its disparity the reference's 0 / 0, which the dump writes as 0.)"""
+    import numpy as np
+    dumps = []
+    for run in range(2):
+        d = tmp_path / ("out%d" % run)
+        line = result_line(run_bench({}, "--steps", "2", "--warmup", "1", "--dump-outputs", str(d)))
+        for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+            assert k in line, k
+        assert line["metric"] == "rays_per_sec" and line["steps"] == 2 and line["dtype"] == "bf16" and line["value"] > 1e6
+        assert abs(line["ms_per_step"] - 160000 / line["value"] * 1e3) < 1e-6 * line["ms_per_step"]
+        assert line["roofline"]["launches"] == 20                  # the timed steps only: two field launches per 32768-ray group
+        for k in ("cpu_baseline", "perturb0", "fp32", "fp32_split", "c5_n1", "c1"):
+            assert k not in line, k
+        dumps.append({f.stem: np.load(f) for f in sorted(d.glob("*.npy"))})
+    a, b = dumps
+    assert sorted(a) == ["acc0", "acc_map", "disp0", "disp_map", "rgb0", "rgb_map", "z_std"], sorted(a)
+    assert a["rgb_map"].shape == (400, 400, 3) and a["acc_map"].shape == (400, 400)
+    for k in a:
+        assert a[k].dtype == np.float32 and np.isfinite(a[k]).all(), k
+        assert np.array_equal(a[k], b[k]), k
+    assert np.array_equal(a["disp_map"] == 0, a["acc_map"] == 0) and np.array_equal(a["disp0"] == 0, a["acc0"] == 0)
 
 
 _RCCL_WORLD1 = r"""

@@ -371,6 +371,41 @@ def test_bench_launches_its_own_ranks_and_fails_cleanly_without_a_gpu():
     assert p.returncode != 0 and "WORLD_SIZE=1" in p.stderr
 
 
+def test_bench_options_and_output_dump(tmp_path, monkeypatch):
+    """A plain run is lean (--full is off by default); dump_outputs writes float32 .npy files, and above the size limit the
+    same fixed seeded rows of every array, with their ray indices."""
+    sys.path.insert(0, REPO)
+    import bench
+    a = bench.parse_args(["--steps", "5"])
+    assert a.steps == 5 and not a.full and a.dump_outputs is None
+    a = bench.parse_args(["--full", "--dump-outputs", "d"])
+    assert a.full and a.dump_outputs == "d"
+    maps = {"rgb_map": torch.rand(6, 10, 3, dtype=torch.float64), "acc_map": torch.rand(6, 10)}
+    bench.dump_outputs(str(tmp_path / "all"), maps, 60)
+    for k, v in maps.items():
+        got = np.load(tmp_path / "all" / (k + ".npy"))
+        assert got.dtype == np.float32 and np.array_equal(got, v.float().numpy()), k
+    assert not (tmp_path / "all" / "ray_index.npy").exists()
+    # the disparity of a ray without weight (acc 0) is the reference's 0 / 0: written as 0; a NaN anywhere else stays visible
+    acc, disp = torch.tensor([0.0, 0.5, 0.0, 1.0]), torch.tensor([float("nan"), float("nan"), 2.0, 0.25])
+    bench.dump_outputs(str(tmp_path / "nan"), {"acc_map": acc, "disp_map": disp, "acc0": acc, "disp0": disp.clone()}, 4)
+    for k in ("disp_map", "disp0"):
+        got = np.load(tmp_path / "nan" / (k + ".npy"))
+        assert got[0] == 0 and np.isnan(got[1]) and list(got[2:]) == [2.0, 0.25], (k, got)
+    assert torch.isnan(disp[0])                                      # the caller's tensor is left as it was
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", 600)               # 60 rays x 16 B (+ 8 B of index) -> 25 rows
+    runs = []
+    for n in range(2):
+        bench.dump_outputs(str(tmp_path / ("s%d" % n)), maps, 60)
+        runs.append({k: np.load(tmp_path / ("s%d" % n) / (k + ".npy")) for k in ("rgb_map", "acc_map", "ray_index")})
+    idx = runs[0]["ray_index"].astype(np.int64)
+    assert len(idx) == 25 and np.all(np.diff(idx) > 0)
+    assert sum(v.nbytes for v in runs[0].values()) <= 600
+    assert np.array_equal(runs[0]["rgb_map"], maps["rgb_map"].float().numpy().reshape(60, 3)[idx])
+    assert np.array_equal(runs[0]["acc_map"][:, 0], maps["acc_map"].float().numpy().reshape(60)[idx])
+    assert all(np.array_equal(runs[0][k], runs[1][k]) for k in runs[0])
+
+
 def test_bench_counts_the_cores_it_is_granted(monkeypatch):
     """cpu_baseline uses every core granted to the process: the affinity mask capped by a cgroup quota."""
     sys.path.insert(0, REPO)

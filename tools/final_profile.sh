@@ -8,7 +8,7 @@ OUT=gpurun_out/final_$TAG
 mkdir -p $OUT
 export TMPDIR=/tmp
 if [ -z "$TRAIN_ONLY" ]; then
-python bench.py > $OUT/bench.json 2> $OUT/bench.err || exit 1
+python bench.py --full > $OUT/bench.json 2> $OUT/bench.err || exit 1
 tail -c 600 $OUT/bench.json
 # kernel trace + stats of the same command (no CPU leg: it only adds host time; no sub-records, so the field kernel's
 # average in the stats is over the metric's own launches -- 10 per view, warm-up included -- and must agree with the
@@ -17,7 +17,7 @@ rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats -- python3 be
 # counters: separate passes, --pmc only
 for C in "FETCH_SIZE" "WRITE_SIZE" "SQ_INSTS_VALU SQ_INSTS_MFMA SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CYCLES" "MfmaUtil" "SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_WAVE_CYCLES" "GRBM_GUI_ACTIVE SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_WAIT_ANY"; do
   N=$(echo $C | tr ' ' '_' | cut -c1-40)
-  rocprofv3 --pmc $C --output-format csv -d $OUT/pmc_$N -- python3 bench.py --steps 3 --warmup 1 --no-cpu-baseline > $OUT/pmc_$N.json 2> $OUT/pmc_$N.err || echo "pmc pass $N failed"
+  rocprofv3 --pmc $C --output-format csv -d $OUT/pmc_$N -- python3 bench.py --steps 3 --warmup 1 --full --no-cpu-baseline > $OUT/pmc_$N.json 2> $OUT/pmc_$N.err || echo "pmc pass $N failed"
 done
 fi
 # the training step: the timed lines -- eager and captured (utils.CapturedTrainStep), bf16 and split precision --
