@@ -52,6 +52,11 @@ extern "C" {
                                    /* product, fp32 accumulate (csrc/mlp_split.hip); needs        */
                                    /* |activation| < 65504                                        */
 
+/* Largest R*S of one NERF_AMD_PREC_FP32_SPLIT training call (nerf_amd_field_forward_train / nerf_amd_field_backward),
+ * 2^23 - 256: the split weight-gradient kernel addresses its [pad_points(P), <= 256] fp16 planes with 32-bit byte offsets
+ * (pad_points(P) * 256 * 2 < 2^32, pad_points(P) = P rounded up to a multiple of 256). */
+#define NERF_AMD_SPLIT_TRAIN_MAX_POINTS 8388352
+
 #define NERF_AMD_MAX_SKIPS 8
 
 int         nerf_amd_abi_version(void);
@@ -191,11 +196,14 @@ int nerf_amd_raw2outputs_backward(const float *raw, int32_t raw_ch, const float 
  *                             weight-gradient products an fp16 (hi, lo) pair, three MFMAs per product, fp32 accumulation;
  *                             dL/draw is scaled by a power of two taken from its own maximum (csrc/split.h) and the scale
  *                             comes off exactly at the end.  Gradients agree with fp32 autograd to ~1e-6 relative.
+ *                             At most NERF_AMD_SPLIT_TRAIN_MAX_POINTS points per call: a larger R*S returns NERF_AMD_EINVAL
+ *                             (checked before the workspace size) -- split such a call into pieces of whole rays.
  *   NERF_AMD_PREC_FP32        exact fp32 (v_mfma_f32_32x32x2_f32 everywhere, csrc/train_f32.hip) for ANY architecture
  *                             nerf_amd_model_create accepts -- what the reference's netdepth / netwidth / skips flags build
  *                             (config_parser.py:18-25); the same gradients (parameters, points / rays, view directions)
- *                             within 1e-6 of fp32 autograd, at the fp32 MFMA rate: the fallback for models outside the
- *                             family above, not a tuned path.  nerf_amd_model_supports_training(m, precision) says which
+ *                             within 1e-6 of fp32 autograd, at the fp32 MFMA rate, and no range limit beyond fp32's (the
+ *                             split pairs need |activation| < 65504): the path for models outside the family above and for
+ *                             models of the family whose values leave fp16's range.  nerf_amd_model_supports_training(m, precision) says which
  *                             precisions a model trains in.
  *   forward_train : the fused forward (explicit pts + viewdirs, or rays + z_vals with pts = o + d z) that also saves every
  *                   layer's activations in `workspace` (nerf_amd_train_workspace bytes, 256-B aligned)

@@ -332,6 +332,16 @@ int train_path(const nerf_amd_model *m, int precision) {
     if (precision == NERF_AMD_PREC_FP32 && train_f32_supported(m->prog)) return 2;
     return 0;
 }
+// NERF_AMD_SPLIT_TRAIN_MAX_POINTS: dw2s_body (backward.hip) builds the buffer resources of its [pad_points(P), ld <= 256] fp16
+// planes and its per-chunk scalar offsets from 32-bit byte counts; one point more and pad_points(P) * 256 * 2 wraps.
+static_assert(pad_points(NERF_AMD_SPLIT_TRAIN_MAX_POINTS) * 256 * 2 < ((int64_t)1 << 32) &&
+              pad_points(NERF_AMD_SPLIT_TRAIN_MAX_POINTS + 1) * 256 * 2 >= ((int64_t)1 << 32), "split training point limit");
+int split_point_limit(int64_t P) {
+    if (P <= NERF_AMD_SPLIT_TRAIN_MAX_POINTS) return NERF_AMD_OK;
+    return fail(NERF_AMD_EINVAL, "NERF_AMD_PREC_FP32_SPLIT training takes at most NERF_AMD_SPLIT_TRAIN_MAX_POINTS = " +
+                std::to_string(NERF_AMD_SPLIT_TRAIN_MAX_POINTS) + " points (2^23 - 256) per call, got R*S = " + std::to_string(P) +
+                " (the weight-gradient kernel's 32-bit buffer offsets): split the call into pieces of whole rays");
+}
 }  // namespace
 
 int nerf_amd_model_supports_training(const nerf_amd_model *m, int precision) {
@@ -377,6 +387,7 @@ int nerf_amd_field_forward_train(const nerf_amd_model *m, const float *pts, cons
     if (R == 0) return NERF_AMD_OK;
     const bool split = precision == NERF_AMD_PREC_FP32_SPLIT;
     const int64_t P = R * S;
+    if (int rc0 = split ? split_point_limit(P) : NERF_AMD_OK) return rc0;
     if ((!pts && (!rays || !z_vals)) || !raw || !workspace || workspace_bytes < train_workspace_bytes(m->prog, P, split))
         return fail(NERF_AMD_EINVAL, "null pointer or workspace too small");
     MlpArgs a;
@@ -427,6 +438,7 @@ int nerf_amd_field_backward(const nerf_amd_model *m, const float *g_raw, const f
     }
     const bool split = precision == NERF_AMD_PREC_FP32_SPLIT;
     if (int rc0 = need_copy(m, split ? NERF_AMD_COPY_BWD_SPLIT : NERF_AMD_COPY_BWD)) return rc0;
+    if (int rc0 = split ? split_point_limit(n_points) : NERF_AMD_OK) return rc0;
     if (!g_raw || !workspace || workspace_bytes < train_workspace_bytes(m->prog, n_points, split))
         return fail(NERF_AMD_EINVAL, "null pointer or workspace too small");
     hipStream_t s = static_cast<hipStream_t>(stream);

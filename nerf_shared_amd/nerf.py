@@ -8,8 +8,9 @@ with ``load_state_dict`` unchanged.
 
 Inference (torch.no_grad(), or nothing requires grad) runs the forward-only kernels.  With
 gradients enabled, the standard model (D=8, W=256, skips=[4]; viewdirs with multires 10/4 or 15/6, or no
-view branch with multires 10 / 15) runs the training kernels -- in bf16, or in split precision (fp32-class
-gradients) when the model's precision is 'fp32_split' or 'fp32' -- and loss.backward() reaches its parameters,
+view branch with multires 10 / 15) runs the training kernels -- in bf16, in split precision (fp32-class
+gradients) when the model's precision is 'fp32_split', or in exact fp32 when it is 'fp32' (as every other
+architecture does) -- and loss.backward() reaches its parameters,
 the points / view directions and the rays.  Any other architecture renders on the
 forward-only kernels and raises NerfAmdError from backward(): outputs never silently come back without
 autograd history.
@@ -34,7 +35,7 @@ def set_default_precision(name):
     architectures it does not cover), 'fp32_split' (fp32-class results from fp16 operand pairs on the 16-bit matrix pipe,
     forward AND backward; needs every encoded input and hidden activation below 65504 in magnitude -- beyond that the fp16
     hi part overflows to inf, which then spreads through the output: use 'fp32' for such models) or 'fp32' (exact-fp32
-    MFMA parity mode; trains on the split-precision kernels, NeRF._train_precision)."""
+    MFMA parity mode, forward AND backward: trains on the exact-fp32 path, NeRF._train_precision)."""
     global _default_precision
     if name not in _PRECISIONS:
         raise ValueError("precision must be one of %s" % sorted(_PRECISIONS))
@@ -238,6 +239,33 @@ class _FieldTrainFn(torch.autograd.Function):
         return (None, None, g_pts, g_vd if (pts is not None and need_vd and g_vd is not None) else None, g_rays, None, None, None) + tuple(grads)
 
 
+# Points per split-precision training call.  The split weight-gradient kernel (csrc/backward.hip dw2s_body) reads its
+# operands -- [pad_points(P), ld] planes of fp16, ld <= 256 slots -- through buffer resources whose record size and
+# per-chunk scalar offsets are 32-bit byte counts: pad_points(P) * 256 * 2 < 2^32, i.e. pad_points(P) <= 2^23 - 256 and so
+# P <= 2^23 - 256.  nerf_amd_field_forward_train / nerf_amd_field_backward refuse larger calls
+# (NERF_AMD_SPLIT_TRAIN_MAX_POINTS, include/nerf_amd.h); NeRF.forward / forward_rays split them into pieces of whole rays.
+_SPLIT_TRAIN_MAX_POINTS = (1 << 23) - 256
+
+
+def _train_field(model, prec, pts, viewdirs, rays, z_vals, n_rays, n_samples):
+    """raw [R*S, ch] of _FieldTrainFn, in pieces of whole rays below _SPLIT_TRAIN_MAX_POINTS for a split-precision call
+    that is larger (each piece its own forward / backward launches; autograd sums the parameter gradients)."""
+    params = model._train_params()
+    if prec != _lib.PREC_FP32_SPLIT or n_rays * n_samples <= _SPLIT_TRAIN_MAX_POINTS:
+        return _FieldTrainFn.apply(model, prec, pts, viewdirs, rays, z_vals, n_rays, n_samples, *params)
+    step = _SPLIT_TRAIN_MAX_POINTS // n_samples
+    if step < 1:
+        raise _lib.NerfAmdError("%d samples per ray exceed the split-precision training limit of %d points per call"
+                                % (n_samples, _SPLIT_TRAIN_MAX_POINTS))
+    raws = []
+    for r0 in range(0, n_rays, step):
+        r1 = min(n_rays, r0 + step)
+        piece = lambda t, k: None if t is None else t[r0 * k:r1 * k]          # noqa: E731
+        raws.append(_FieldTrainFn.apply(model, prec, piece(pts, n_samples), piece(viewdirs, 1), piece(rays, 1),
+                                        piece(z_vals, 1), r1 - r0, n_samples, *params))
+    return torch.cat(raws, 0)
+
+
 # The packed device copy of a model's weights is refreshed when a parameter's (data_ptr, _version)
 # changes.  Optimizers that update through fused multi-tensor kernels (torch.optim.Adam(fused=True))
 # do not bump `_version`, so every optimizer step also marks the models it updated stale.  Writes through
@@ -308,7 +336,9 @@ class NeRF(nn.Module):
 
     def weights_changed(self):
         """Force a re-pack of the parameters on the next call (needed only after writing through
-        `param.data` or other paths that bypass autograd's version counters)."""
+        `param.data` or other paths that bypass autograd's version counters and the optimizer's post-step hooks -- a
+        replayed graph that steps the optimizer is one: after each replay of a graph captured by hand, call the
+        optimizer's note_replayed_step() (nerf_shared_amd.optim.Adam; utils.CapturedTrainStep does) or this)."""
         self._packed_key = None
 
     # -- device-side packed copy of the parameters --------------------------------
@@ -409,10 +439,8 @@ class NeRF(nn.Module):
             return "none", None
         prec = self.precision or _default_precision
         self._ensure_handle(device)
-        if self.__dict__['_trainable_kernels']:
-            return "train", None
-        if self.__dict__['_trainable_f32']:
-            return "train", None           # any other architecture: the exact-fp32 training path (csrc/train_f32.hip)
+        if self._train_precision() != _lib.PREC_FP32 or self.__dict__['_trainable_f32']:
+            return "train", None           # (the exact-fp32 path, csrc/train_f32.hip, needs its feature rows to fit the CU's LDS)
         msg = ("backward() reached a result of the forward-only kernels: this model is %s(D=%d, W=%d, skips=%s, use_viewdirs=%s, "
                "multires=%d, multires_views=%d, output_ch=%d) in precision '%s', and neither the fused training kernels (NeRF(D=8, "
                "W=256, skips=[4]), multires 10/4, 15/6, or 10 / 15 without view branch) nor the exact-fp32 training path (its "
@@ -423,16 +451,17 @@ class NeRF(nn.Module):
         return "defer", (anchor, msg)
 
     def _train_precision(self):
-        """Arithmetic of the training kernels for this model's precision: 'bf16' trains in bf16; 'fp32_split' AND 'fp32'
-        train on the split-precision kernels (fp16 operand pairs, three MFMAs per product -- forward, dX chain and weight
-        gradients; gradients agree with fp32 autograd to ~1e-6): an 'fp32' model of the fused family has the split-precision
-        training forward (1e-5 from its exact inference forward on |raw| <= 20).  Every other architecture trains on the
-        exact-fp32 path (csrc/train_f32.hip: fp32 MFMA rate)."""
+        """Arithmetic of the training kernels for this model's precision.  In the fused 8 x 256 family 'bf16' trains in
+        bf16 and 'fp32_split' on the split-precision kernels (fp16 operand pairs, three MFMAs per product -- forward, dX
+        chain and weight gradients; gradients agree with fp32 autograd to ~1e-6, as long as every encoded input and hidden
+        activation stays below fp16's 65504).  'fp32' trains on the exact-fp32 path (csrc/train_f32.hip: fp32 MFMA rate, no
+        range limit beyond fp32's) on every architecture, and so does every architecture outside the fused family, whatever
+        its inference precision."""
         name = self.precision or _default_precision
         if name not in _PRECISIONS:
             raise ValueError("precision must be one of %s" % sorted(_PRECISIONS))
-        if not self.__dict__.get('_trainable_kernels', True):
-            return _lib.PREC_FP32          # not the fused family: the exact-fp32 training path, whatever the inference precision
+        if name == "fp32" or not self.__dict__.get('_trainable_kernels', True):
+            return _lib.PREC_FP32
         return _lib.PREC_BF16 if name == "bf16" else _lib.PREC_FP32_SPLIT
 
     def _wants_grad(self, device, *inputs):
@@ -443,7 +472,7 @@ class NeRF(nn.Module):
         """raw [R, S, 4] of rays [R, 11] at depths z_vals [R, S] (pts = o + d z formed in the kernel);
         differentiable with respect to the parameters and the ray batch."""
         R, S = z_vals.shape
-        raw = _FieldTrainFn.apply(self, self._train_precision(), None, None, rays, z_vals, R, S, *self._train_params())
+        raw = _train_field(self, self._train_precision(), None, None, rays, z_vals, R, S)
         return raw.reshape(R, S, 4 if self.use_viewdirs else self.output_ch)
 
     def _precision_code(self):
@@ -484,7 +513,7 @@ class NeRF(nn.Module):
         out_ch = 4 if self.use_viewdirs else self.output_ch
         n_rays = pts.shape[0] // n_samples
         if want:
-            raw = _FieldTrainFn.apply(self, self._train_precision(), pts, vd, None, None, n_rays, n_samples, *self._train_params())
+            raw = _train_field(self, self._train_precision(), pts, vd, None, None, n_rays, n_samples)
             return raw.reshape(list(inputs.shape[:-1]) + [out_ch])
         handle = self._model_handle(dev)
         out = torch.empty(pts.shape[0], out_ch, device=dev, dtype=torch.float32)

@@ -16,7 +16,7 @@ import ctypes
 
 import torch
 
-from . import _lib
+from . import _lib, nerf
 from ._lib import lib
 
 
@@ -60,9 +60,13 @@ class Adam(torch.optim.Adam):
             lr_dev.fill_(float(self.param_groups[gi]["lr"]))
 
     def note_replayed_step(self, n=1):
-        """A captured step() was replayed n times: the host-side counts (state_dict(), checkpoints) follow the device's."""
+        """A captured step() was replayed n times: the host-side counts (state_dict(), checkpoints) follow the device's, and
+        every NeRF whose parameters this optimizer steps is marked stale -- a replay updates the parameters on the device
+        without bumping their `_version` and without running the optimizer's post-step hooks, so the packed copies an eager
+        render reads would otherwise keep the weights of the last eager pack."""
         for c in self._together.values():
             c["step"] += n
+        nerf._after_optimizer_step(self, (), {})
 
     # -- torch.optim.Optimizer surface -------------------------------------------
     def __getstate__(self):

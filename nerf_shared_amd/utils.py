@@ -293,7 +293,10 @@ class CapturedTrainStep:
         next call picks it up; the optimizer's step count advances on the device and is mirrored on the host;
       * gradients are left in `.grad` after every call (the captured step starts from zeroed gradients, like
         optimizer.zero_grad() at the top of the loop body);
-      * random draws (perturb, raw_noise_std) advance with every replay (torch's graph-safe generator offsets).
+      * random draws (perturb, raw_noise_std) advance with every replay (torch's graph-safe generator offsets);
+      * every replay marks the stepped models' packed weights stale (optimizer.note_replayed_step()), so an eager render
+        between calls (main.py's i_img / i_testset) sees the latest step.  A graph captured by hand around
+        optimizer.step() must do the same after each replay: optimizer.note_replayed_step(), or model.weights_changed().
     Everything the step touches must stay alive and in place (models, optimizer state).  Needs nerf_shared_amd.optim.Adam
     (utils.get_optimizer) and models the training kernels cover.  Constructing it leaves parameters, moments and step
     counts as they were (the warm-up steps the capture needs are undone).

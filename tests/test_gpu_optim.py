@@ -272,8 +272,71 @@ def test_captured_train_step_equals_the_eager_loop(dev, precision):
         assert float((a - b).norm() / b.norm().clamp_min(1e-30)) < (2e-3 if precision == "bf16" else 2e-5)
     assert gopt._together[0]["step"] == steps == int(gopt.state_dict()["state"][0]["step"])
     assert np.isfinite(float(step.psnr))
-    # inference after the captured steps sees the updated weights (the pack is marked stale by every replay)
+    # one render after all the replays sees the updated weights (the capture leaves the models' pack key unset, so the first
+    # eager render re-packs; renders BETWEEN replays are test_render_between_replays_sees_the_latest_step)
     with torch.no_grad():
         a = r.render_from_rays(400, 400, K, 32768, batches[0][0], gc, gf, retraw=False)[0]
         b = r.render_from_rays(400, 400, K, 32768, batches[0][0], mc, mf, retraw=False)[0]
     assert float((a - b).abs().max()) < (5e-2 if precision == "bf16" else 1e-3)
+
+
+@pytest.mark.parametrize("precision", ["bf16", "fp32_split", "fp32", "fp32_small_architecture"])
+def test_render_between_replays_sees_the_latest_step(dev, precision):
+    """main.py's i_img / i_testset pattern with utils.CapturedTrainStep: eager no_grad renders (rgb and raw) of a fixed ray batch between
+    replays -- one round with two replays in a row, one with an eager training forward / backward (zero_grad, no step)
+    between replays -- equal, bit for bit, the same render by fresh NeRFs loaded with the captured models' current
+    state_dict: a replay updates the parameters on the device behind autograd's version counters, and every replay must
+    mark the packed copies stale (optim.Adam.note_replayed_step)."""
+    from nerf_shared_amd import nerf, optim, render_utils, synth, utils
+    arch = dict(D=8, W=256, output_ch=5, skips=[4], use_viewdirs=True, multires=10, multires_views=4)
+    if precision == "fp32_small_architecture":             # netdepth 4, netwidth 128: the exact-fp32 training path (train_f32.hip)
+        arch, precision = dict(arch, D=4, W=128, skips=[2]), "fp32"
+    cfg = dict(perturb=0.0, N_importance=32, N_samples=32, use_viewdirs=True, white_bkgd=True, raw_noise_std=0.0, near=2.0, far=6.0)
+    K = synth.lego_intrinsics(400, 400)
+    rng = np.random.default_rng(8)
+    N = 256
+
+    def batch():
+        idx = rng.choice(160000, size=N, replace=False)
+        ro, rd = synth.rays_np(400, 400, K, synth.LEGO_C2W, idx)
+        return (torch.from_numpy(np.stack([ro, rd], 0)).to(dev),
+                torch.from_numpy(rng.uniform(0, 1, size=(N, 3)).astype(np.float32)).to(dev))
+
+    def make(sds):
+        ms = []
+        for sd in sds:
+            m = nerf.NeRF(**arch)
+            m.load_state_dict(sd)
+            m.precision = precision
+            ms.append(m.to(dev))
+        return ms
+
+    mc, mf = make([synth.torch_state_dict(seed, 1.0, **{**arch, "skips": tuple(arch["skips"])}) for seed in (0, 10)])
+    opt = optim.Adam(list(mc.parameters()) + list(mf.parameters()), lr=1e-3, betas=(0.9, 0.999))
+    r = render_utils.Renderer(**cfg)
+    step = utils.CapturedTrainStep(r, 400, 400, K, 32768, mc, mf, opt, N)
+    view = batch()[0]
+
+    def render(c, f):                                      # rgb and the fine pass's raw (rgb alone saturates to white here)
+        with torch.no_grad():
+            rgb, _, _, extras = r.render_from_rays(400, 400, K, 32768, view, c, f, retraw=True)
+        return torch.cat([rgb.flatten(), extras["raw"].flatten()])
+
+    before = render(mc, mf)
+    # R: one replay; E: an eager training pass (forward, backward, zero_grad -- no optimizer step)
+    for rnd, plan in enumerate(["R", "R", "RR", "RER", "R"]):
+        for what in plan:
+            if what == "R":
+                step(*batch())
+                continue
+            rays, tgt = batch()
+            rgb, _, _, ex = r.render_from_rays(400, 400, K, 32768, rays, mc, mf, retraw=True)
+            (utils.img2mse(rgb, tgt) + utils.img2mse(ex["rgb0"], tgt)).backward()
+            opt.zero_grad()
+        got = render(mc, mf)
+        fc, ff = make([{k: v.detach().clone() for k, v in m.state_dict().items()} for m in (mc, mf)])
+        want = render(fc, ff)
+        print("round %d: max |render - fresh twin| = %.3e" % (rnd, float((got - want).abs().max())))
+        assert torch.equal(got, want), rnd
+        assert not torch.equal(got, before), "degenerate test: the replays did not change the render"
+        before = got

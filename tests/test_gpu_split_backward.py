@@ -1,5 +1,6 @@
-"""GPU tests (-m gpu) of the split-precision backward pass (precision "fp32_split" / "fp32": csrc/mlp_split.hip SAVE,
-mlp_bwd_split.hip, backward.hip dw2s_body) against torch.autograd on the PLAIN fp32 oracle -- no rounding model.
+"""GPU tests (-m gpu) of the split-precision backward pass (precision "fp32_split": csrc/mlp_split.hip SAVE,
+mlp_bwd_split.hip, backward.hip dw2s_body) and of the fused family's "fp32" training (the exact-fp32 path, csrc/train_f32.hip)
+against torch.autograd on the PLAIN fp32 oracle -- no rounding model.
 
 The reference trains and pose-optimises in fp32 (main.py:85-104, demo_est_rel_pose.py:87-98); these are the gates that say
 the build does too: relative L2 <= 1e-3 and cosine >= 0.9999 for every parameter tensor and for the ray gradients
@@ -68,17 +69,15 @@ def assert_table(table, gate_rel=GATE_REL, gate_cos=GATE_COS):
         assert e < gate_rel and c > gate_cos, (name, e, c)
 
 
-@pytest.mark.parametrize("precision", ["fp32_split", "fp32"])
-@pytest.mark.parametrize("seed,sharpen,arch", [(0, 1.0, VD), (1, 2.0, VD), (2, 1.0, VD15), (3, 1.0, NOVD), (4, 2.0, NOVD4), (5, 1.0, NOVD15)],
-                         ids=["vd_s0", "vd_x2", "vd_15_6", "novd", "novd_out4_x2", "novd_15_out13"])
-def test_field_backward_matches_fp32_autograd(dev, seed, sharpen, arch, precision):
-    """dL/dtheta of NeRF.forward for a random linear loss on raw, every architecture the training kernels cover, against
-    torch.autograd on the fp32 oracle.  The training forward's values pass the fp32 forward gate and are bit-identical to
-    the split-precision inference kernel's."""
-    if precision == "fp32" and arch is not VD:
-        pytest.skip("'fp32' trains on the same kernels as 'fp32_split': one architecture is enough")
+FIELD_CASES = [(0, 1.0, VD), (1, 2.0, VD), (2, 1.0, VD15), (3, 1.0, NOVD), (4, 2.0, NOVD4), (5, 1.0, NOVD15)]
+FIELD_IDS = ["vd_s0", "vd_x2", "vd_15_6", "novd", "novd_out4_x2", "novd_15_out13"]
+
+
+def field_run(dev, seed, sharpen, arch, precision):
+    """NeRF.forward under autograd for a random linear loss on raw (70 rays x 13 samples: 910 points, ragged), and the
+    same on the fp32 oracle: (model, oracle state with gradients, training forward's raw, oracle raw, pts, vd)."""
     rng = np.random.default_rng(11)
-    R, S = 70, 13                                   # 910 points: ragged
+    R, S = 70, 13
     pts = torch.from_numpy(rng.uniform(-2, 2, size=(R, S, 3)).astype(np.float32))
     vd = torch.from_numpy(rng.normal(size=(R, 3)).astype(np.float32))
     vd = vd / vd.norm(dim=-1, keepdim=True)
@@ -91,6 +90,17 @@ def test_field_backward_matches_fp32_autograd(dev, seed, sharpen, arch, precisio
     out = m(pts.to(dev), vd.to(dev) if vd is not None else None)
     assert out.requires_grad
     (out * coef.to(dev)).sum().backward()
+    return m, cpu, out, ref, pts, vd
+
+
+@pytest.mark.parametrize("precision", ["fp32_split"])
+@pytest.mark.parametrize("seed,sharpen,arch", FIELD_CASES, ids=FIELD_IDS)
+def test_field_backward_matches_fp32_autograd(dev, seed, sharpen, arch, precision):
+    """dL/dtheta of NeRF.forward for a random linear loss on raw, every architecture the training kernels cover, against
+    torch.autograd on the fp32 oracle.  The training forward's values pass the fp32 forward gate and are bit-identical to
+    the split-precision inference kernel's.  ('fp32' trains on the exact-fp32 path:
+    test_fp32_field_backward_on_the_exact_path_matches_fp32_autograd.)"""
+    m, cpu, out, ref, pts, vd = field_run(dev, seed, sharpen, arch, precision)
     np.testing.assert_allclose(out.detach().cpu().numpy(), ref.detach().numpy(), atol=1e-4, rtol=1e-4)
     with torch.no_grad():
         m.precision = "fp32_split"
@@ -98,6 +108,22 @@ def test_field_backward_matches_fp32_autograd(dev, seed, sharpen, arch, precisio
     table = []
     check_params("", m, cpu, table)
     assert_table(table)
+
+
+@pytest.mark.parametrize("seed,sharpen,arch", FIELD_CASES, ids=FIELD_IDS)
+def test_fp32_field_backward_on_the_exact_path_matches_fp32_autograd(dev, seed, sharpen, arch):
+    """The same in 'fp32', which trains on the exact-fp32 path (csrc/train_f32.hip, NeRF._train_precision) on every
+    architecture: the training forward passes the fp32 forward gate and is bit-identical to the model's own 'fp32' inference
+    output (the exact kernel: train_f32's forward is mlp_fp32.hip's layer loop), and the gradients pass the exact path's gate,
+    2e-5 relative L2 (test_gpu_train_f32.py), not the split gate."""
+    m, cpu, out, ref, pts, vd = field_run(dev, seed, sharpen, arch, "fp32")
+    np.testing.assert_allclose(out.detach().cpu().numpy(), ref.detach().numpy(), atol=1e-4, rtol=1e-4)
+    with torch.no_grad():
+        inference = m(pts.to(dev), vd.to(dev) if vd is not None else None)
+    torch.testing.assert_close(inference, out.detach(), rtol=0, atol=0)
+    table = []
+    check_params("", m, cpu, table)
+    assert_table(table, gate_rel=2e-5)
 
 
 def oracle_two_pass(cfg, batch, coarse, fine, z_fine, pytest_draws=False):
@@ -555,3 +581,198 @@ def test_field_backward_on_awkward_point_counts(dev, n_points):
     table = []
     check_params("", m, cpu, table)
     assert_table(table)
+
+
+def scaled_models(dev, seed, arch, precision, k):
+    """models() with the first layer's weight and bias times k: every hidden unit of layer 0 (and its ReLU output) scales
+    by k exactly."""
+    from nerf_shared_amd import nerf
+    sd = synth.torch_state_dict(seed, 1.0, **{**arch, "skips": (4,)})
+    for name in ("pts_linears.0.weight", "pts_linears.0.bias"):
+        sd[name] = sd[name] * k
+    m = nerf.NeRF(**arch)
+    m.load_state_dict(sd)
+    m = m.to(dev)
+    m.precision = precision
+    cpu = {k_: v.clone().requires_grad_(True) for k_, v in O.state_dict_to_torch(sd).items()}
+    return m, cpu
+
+
+@pytest.mark.parametrize("arch", [VD, NOVD], ids=["viewdirs", "output_linear"])
+def test_fp32_trains_beyond_the_fp16_range(dev, arch):
+    """The case 'fp32' exists for (set_default_precision): a fused-family model whose first hidden layer, after its ReLU,
+    reaches 1e5 on the oracle -- beyond fp16's 65504, so the split kernels' hi parts overflow.  In 'fp32' the training
+    forward passes the fp32 forward gate (rel-L2 1e-5 against the oracle) and the parameter, point and view-direction
+    gradients are finite and within 2e-5 of fp32 autograd; the same model in 'fp32_split' fails that forward gate (non-finite
+    output counts as failing), which keeps the documented limit honest and shows the case really is out of fp16's range."""
+    vdirs = bool(arch["use_viewdirs"])
+    rng = np.random.default_rng(31)
+    R, S = 60, 11
+    pts = torch.from_numpy(rng.uniform(-2, 2, size=(R, S, 3)).astype(np.float32))
+    vd = torch.from_numpy(rng.normal(size=(R, 3)).astype(np.float32)) if vdirs else None
+    out_ch = 4 if vdirs else arch["output_ch"]
+    coef = torch.from_numpy(rng.normal(size=(R, S, out_ch)).astype(np.float32))
+    m, cpu = scaled_models(dev, 6, arch, "fp32", 1e5)
+    with torch.no_grad():
+        h0 = torch.relu(O._lin(cpu, "pts_linears.0", O.embed(pts.reshape(-1, 3), arch["multires"])))
+    print("largest post-ReLU activation of layer 0 on the oracle: %.3e" % float(h0.max()))
+    assert float(h0.max()) > 1e5, "degenerate test: the model is inside fp16's range"
+    p_cpu = pts.clone().requires_grad_(True)
+    v_cpu = vd.clone().requires_grad_(True) if vdirs else None
+    ref = O.nerf_forward(cpu, O.Arch(**arch), p_cpu, v_cpu)
+    (ref * coef).sum().backward()
+    p_gpu = pts.to(dev).requires_grad_(True)
+    v_gpu = vd.to(dev).requires_grad_(True) if vdirs else None
+    out = m(p_gpu, v_gpu)
+    (out * coef.to(dev)).sum().backward()
+    e_fwd = rel_err(out.detach().cpu(), ref.detach())
+    table = [("pts", rel_err(p_gpu.grad.cpu(), p_cpu.grad), cosine(p_gpu.grad, p_cpu.grad))]
+    assert torch.isfinite(p_gpu.grad).all()
+    if vdirs:
+        assert torch.isfinite(v_gpu.grad).all()
+        table.append(("viewdirs", rel_err(v_gpu.grad.cpu(), v_cpu.grad), cosine(v_gpu.grad, v_cpu.grad)))
+    check_params("", m, cpu, table)
+    print("'fp32' forward rel-L2 vs the oracle %.3e" % e_fwd)
+    assert e_fwd <= 1e-5
+    assert_table(table, gate_rel=2e-5)
+    # the same model in split precision: out of its range
+    ms, _ = scaled_models(dev, 6, arch, "fp32_split", 1e5)
+    out_s = ms(pts.to(dev).requires_grad_(True), vd.to(dev) if vdirs else None).detach().cpu()
+    finite = bool(torch.isfinite(out_s).all())
+    e_split = rel_err(out_s, ref.detach()) if finite else float("inf")
+    print("'fp32_split' forward: finite %s, rel-L2 vs the oracle %.3e" % (finite, e_split))
+    assert not (finite and e_split <= 1e-5), "fp32_split passed the fp32 gate beyond fp16's range"
+
+
+def test_split_training_point_limit_is_refused_before_the_workspace_check(dev):
+    """nerf_amd_field_forward_train / nerf_amd_field_backward in NERF_AMD_PREC_FP32_SPLIT refuse more than
+    NERF_AMD_SPLIT_TRAIN_MAX_POINTS = 2^23 - 256 points (the weight-gradient kernel's 32-bit buffer offsets would wrap), before
+    they look at the workspace: with a 1-byte workspace the limit itself fails on 'workspace too small', one point more on
+    the limit.  Nothing of that size is allocated and no kernel runs (both calls return before any launch)."""
+    import ctypes
+    import re
+
+    from nerf_shared_amd import _lib, nerf
+    lim = nerf._SPLIT_TRAIN_MAX_POINTS
+    assert lim == (1 << 23) - 256
+    with open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "include", "nerf_amd.h")) as f:
+        assert int(re.search(r"#define NERF_AMD_SPLIT_TRAIN_MAX_POINTS\s+(\d+)", f.read()).group(1)) == lim
+    m, _ = models(dev, 0, 1.0, VD, "fp32_split")
+    h = m._model_handle(dev, _lib.TRAIN_COPIES[_lib.PREC_FP32_SPLIT] | _lib.TRAIN_COPIES[_lib.PREC_BF16])
+    buf = torch.zeros(64, device=dev)             # stands in for every array: no call below reads or writes it
+    ws = torch.empty(1, dtype=torch.uint8, device=dev)
+    n = len(m._grad_layout()[1])
+    gw = (ctypes.c_void_p * n)(*[buf.data_ptr()] * n)
+    gb = (ctypes.c_void_p * n)(*[buf.data_ptr()] * n)
+    stream = _lib.stream_of(dev)
+
+    def calls(P, prec):
+        b = buf.data_ptr()
+        fwd = _lib.lib.nerf_amd_field_forward_train(h, b, b, None, 0, None, P, 1, b, ws.data_ptr(), ws.numel(), prec, stream)
+        fwd_msg = _lib.lib.nerf_amd_last_error().decode()
+        bwd = _lib.lib.nerf_amd_field_backward(h, b, b, b, None, 0, None, P, 1, ws.data_ptr(), ws.numel(), gw, gb, n,
+                                               None, None, None, prec, stream)
+        bwd_msg = _lib.lib.nerf_amd_last_error().decode()
+        return (fwd, fwd_msg), (bwd, bwd_msg)
+
+    for rc, msg in calls(lim, _lib.PREC_FP32_SPLIT):
+        assert rc == -1 and "workspace too small" in msg, msg
+    for rc, msg in calls(lim + 1, _lib.PREC_FP32_SPLIT):
+        assert rc == -1 and "NERF_AMD_SPLIT_TRAIN_MAX_POINTS = %d" % lim in msg and "workspace" not in msg, msg
+    for rc, msg in calls(lim + 1, _lib.PREC_BF16):                 # the bf16 kernels address with 64 bits: no such limit
+        assert rc == -1 and "workspace too small" in msg, msg
+    torch.cuda.synchronize()
+
+
+def _split_field_run(dev, arch, pts, vd, coef):
+    m, cpu = models(dev, 3, 2.0, arch, "fp32_split")
+    p_gpu = pts.to(dev).requires_grad_(True)
+    v_gpu = vd.to(dev).requires_grad_(True) if vd is not None else None
+    out = m(p_gpu, v_gpu)
+    (out * coef.to(dev)).sum().backward()
+    grads = {name: p.grad.detach().clone() for name, p in m.named_parameters() if p.grad is not None}
+    grads["pts"] = p_gpu.grad.detach().clone()
+    if v_gpu is not None:
+        grads["viewdirs"] = v_gpu.grad.detach().clone()
+    return out.detach(), grads, m, cpu
+
+
+@pytest.mark.parametrize("arch", [VD, NOVD], ids=["viewdirs", "output_linear"])
+def test_split_training_above_the_point_limit_runs_in_pieces_of_whole_rays(dev, arch, monkeypatch):
+    """NeRF.forward in 'fp32_split' with more points than nerf._SPLIT_TRAIN_MAX_POINTS (lowered here to 300, so that 70 rays of
+    13 samples go in pieces of 23 rays, the last one ragged): raw bit-identical to the call in one piece, parameter / point /
+    view-direction gradients within the split gates of fp32 autograd on the oracle and within 1e-5 of the one-piece run
+    (each piece takes its own loss scale, so they are not bit-identical)."""
+    from nerf_shared_amd import nerf
+    rng = np.random.default_rng(11)
+    R, S = 70, 13
+    pts = torch.from_numpy(rng.uniform(-2, 2, size=(R, S, 3)).astype(np.float32))
+    vd = torch.from_numpy(rng.normal(size=(R, 3)).astype(np.float32))
+    vd = vd / vd.norm(dim=-1, keepdim=True)
+    if not arch["use_viewdirs"]:
+        vd = None
+    coef = torch.from_numpy(rng.normal(size=(R, S, 4 if arch["use_viewdirs"] else arch["output_ch"])).astype(np.float32))
+    raw1, g1, _, _ = _split_field_run(dev, arch, pts, vd, coef)
+    monkeypatch.setattr(nerf, "_SPLIT_TRAIN_MAX_POINTS", 300)
+    calls = []
+    real_apply = nerf._FieldTrainFn.apply
+    monkeypatch.setattr(nerf._FieldTrainFn, "apply", lambda *a: calls.append(a[6] * a[7]) or real_apply(*a))
+    raw2, g2, m, cpu = _split_field_run(dev, arch, pts, vd, coef)
+    assert calls == [299, 299, 299, 13], calls
+    assert torch.equal(raw2, raw1)
+    p_cpu = pts.clone().requires_grad_(True)
+    v_cpu = vd.clone().requires_grad_(True) if vd is not None else None
+    (O.nerf_forward(cpu, O.Arch(**arch), p_cpu, v_cpu) * coef).sum().backward()
+    table = [("pts", rel_err(g2["pts"], p_cpu.grad), cosine(g2["pts"], p_cpu.grad))]
+    if vd is not None:
+        table.append(("viewdirs", rel_err(g2["viewdirs"], v_cpu.grad), cosine(g2["viewdirs"], v_cpu.grad)))
+    check_params("", m, cpu, table)
+    assert_table(table)
+    for name in g1:
+        e = rel_err(g2[name], g1[name])
+        assert e < 1e-5, (name, e)
+
+
+def test_split_training_step_above_the_point_limit_runs_in_pieces_of_whole_rays(dev, monkeypatch):
+    """The two-pass training loss of Renderer.render_rays (rays mode: pts = o + d z in the kernel) in 'fp32_split' with the
+    point limit lowered to 500 (coarse pass: pieces of 15 rays x 32 samples, fine pass: 6 rays x 80; 80 rays): raw and depths
+    bit-identical to the run in one piece; parameter and ray gradients within the split gates of fp32 autograd on the oracle
+    (fine pass on the run's own depths) and within 1e-5 of the one-piece run."""
+    from nerf_shared_amd import nerf, render_utils
+    batch, target = _batch(80, 7)                   # test_ray_gradients_for_pose_estimation_match_fp32_autograd's rays
+    cfg = dict(BASE, N_samples=32, N_importance=48)
+    r = render_utils.Renderer(**cfg)
+
+    def assemble(o, d):
+        return torch.cat([o, d, 2.0 * torch.ones_like(d[:, :1]), 6.0 * torch.ones_like(d[:, :1]),
+                          d / torch.norm(d, dim=-1, keepdim=True)], -1)
+
+    def run():
+        mc, cc = models(dev, 1, 2.0, VD, "fp32_split")
+        mf, cf = models(dev, 11, 2.0, VD, "fp32_split")
+        ro = batch[:, 0:3].clone().to(dev).requires_grad_(True)
+        rd = (batch[:, 3:6] * 1.3).clone().to(dev).requires_grad_(True)
+        out = r.render_rays(assemble(ro, rd), mc, mf, retraw=True, retweights=True)
+        t = target.to(dev)
+        (((out["rgb_map"] - t) ** 2).mean() + ((out["rgb0"] - t) ** 2).mean()).backward()
+        grads = {"coarse." + k: p.grad.detach().clone() for k, p in mc.named_parameters() if p.grad is not None}
+        grads.update({"fine." + k: p.grad.detach().clone() for k, p in mf.named_parameters() if p.grad is not None})
+        grads.update(rays_o=ro.grad.detach().clone(), rays_d=rd.grad.detach().clone())
+        return out, grads, (mc, cc), (mf, cf)
+
+    out1, g1, _, _ = run()
+    monkeypatch.setattr(nerf, "_SPLIT_TRAIN_MAX_POINTS", 500)
+    out2, g2, (mc, cc), (mf, cf) = run()
+    assert torch.equal(out2["raw"], out1["raw"]) and torch.equal(out2["z_vals"], out1["z_vals"])
+    o = batch[:, 0:3].clone().requires_grad_(True)
+    d = (batch[:, 3:6] * 1.3).clone().requires_grad_(True)
+    rgb, rgb0 = oracle_two_pass(cfg, assemble(o, d), (cc, O.Arch(**VD)), (cf, O.Arch(**VD)), out2["z_vals"].detach().cpu())
+    (((rgb - target) ** 2).mean() + ((rgb0 - target) ** 2).mean()).backward()
+    table = [("rays_o", rel_err(g2["rays_o"], o.grad), cosine(g2["rays_o"], o.grad)),
+             ("rays_d", rel_err(g2["rays_d"], d.grad), cosine(g2["rays_d"], d.grad))]
+    check_params("coarse.", mc, cc, table)
+    check_params("fine.", mf, cf, table)
+    assert_table(table)
+    for name in g1:
+        e = rel_err(g2[name], g1[name])
+        assert e < 1e-5, (name, e)

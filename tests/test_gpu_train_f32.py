@@ -131,14 +131,18 @@ def test_training_step_and_adam_on_a_small_architecture(dev):
     np.testing.assert_allclose(losses, ref, rtol=2e-3)
 
 
-@pytest.mark.parametrize("name", ["d4_w128_skip2", "d6_w96_skips13", "d8_w256_identity_embed", "d2_w64_noskip_novd"])
+# the fused 8 x 256 family in 'fp32' trains on the exact-fp32 path too (NeRF._train_precision)
+FUSED = {"d8_w256_fused_vd": dict(D=8, W=256, output_ch=5, skips=[4], use_viewdirs=True, multires=10, multires_views=4)}
+
+
+@pytest.mark.parametrize("name", ["d4_w128_skip2", "d6_w96_skips13", "d8_w256_identity_embed", "d2_w64_noskip_novd", "d8_w256_fused_vd"])
 def test_point_and_ray_gradients_of_any_architecture(dev, name):
-    """Pose estimation on a model outside the fused family (demo_est_rel_pose.py:87-98): dL/d(points, view directions) of the
-    field, and dL/d(rays_o, rays_d) through Renderer.render_rays with frozen networks, against fp32 autograd on the oracle
-    (fine pass on the run's own depths)."""
+    """Pose estimation on a model in 'fp32' (demo_est_rel_pose.py:87-98) -- outside the fused family, or the fused 8 x 256 viewdirs
+    model itself: dL/d(points, view directions) of the field, and dL/d(rays_o, rays_d) through Renderer.render_rays with
+    frozen networks, against fp32 autograd on the oracle (fine pass on the run's own depths)."""
     from nerf_shared_amd import render_utils
     from test_gpu_split_backward import oracle_two_pass
-    arch = ARCHS[name]
+    arch = {**ARCHS, **FUSED}[name]
     vdirs = arch["use_viewdirs"]
     rng = np.random.default_rng(21)
     pts = torch.from_numpy(rng.uniform(-2, 2, size=(40, 9, 3)).astype(np.float32))

@@ -488,6 +488,47 @@ def test_packed_weights_go_stale_after_optimizer_steps_and_copies_get_their_own_
     assert torch.equal(c.pts_linears[3].weight, m.pts_linears[3].weight)
 
 
+def test_a_replayed_optimizer_step_marks_its_models_stale():
+    """A replayed captured step updates the parameters on the device without bumping `_version` and without running the
+    optimizer's post-step hooks: optim.Adam.note_replayed_step() (called after every replay) marks the models whose
+    parameters the optimizer steps stale -- and only those."""
+    from nerf_shared_amd import optim
+    m = nerf.NeRF(D=8, W=256, output_ch=5, skips=[4], use_viewdirs=True)
+    other = nerf.NeRF(D=8, W=256, output_ch=5, skips=[4], use_viewdirs=True)
+    opt = optim.Adam(m.parameters(), lr=1e-3)
+    m._packed_key, other._packed_key = "packed", "packed"
+    opt.note_replayed_step()
+    assert m._packed_key is None and other._packed_key == "packed"
+    m._packed_key = "packed"
+    opt.note_replayed_step(3)
+    assert m._packed_key is None and other._packed_key == "packed"
+
+
+def test_training_precision_of_each_precision_name():
+    """NeRF._train_precision: in the fused family 'bf16' trains in bf16, 'fp32_split' on the split-precision kernels and
+    'fp32' on the exact-fp32 path (no fp16 range limit); outside the family every name trains in exact fp32."""
+    m = nerf.NeRF(D=8, W=256, output_ch=5, skips=[4], use_viewdirs=True)
+    m.__dict__['_trainable_kernels'] = m.__dict__['_trainable_f32'] = True
+    want = {"bf16": _lib.PREC_BF16, "fp32_split": _lib.PREC_FP32_SPLIT, "fp32": _lib.PREC_FP32}
+    for name, code in want.items():
+        m.precision = name
+        assert m._train_precision() == code, name
+    m.__dict__['_trainable_kernels'] = False
+    for name in want:
+        m.precision = name
+        assert m._train_precision() == _lib.PREC_FP32, name
+
+
+def test_split_training_point_limit_matches_the_header():
+    """nerf._SPLIT_TRAIN_MAX_POINTS (where NeRF.forward / forward_rays split a split-precision training call) is the C
+    library's NERF_AMD_SPLIT_TRAIN_MAX_POINTS, 2^23 - 256: pad_points(P) * 256 * 2 bytes still fit 32 bits."""
+    with open(os.path.join(REPO, "include", "nerf_amd.h")) as f:
+        c_limit = int(re.search(r"#define NERF_AMD_SPLIT_TRAIN_MAX_POINTS\s+(\d+)", f.read()).group(1))
+    assert nerf._SPLIT_TRAIN_MAX_POINTS == c_limit == (1 << 23) - 256
+    pad = lambda p: (p + 255) // 256 * 256                  # noqa: E731  (kernels.h pad_points)
+    assert pad(c_limit) * 256 * 2 < 1 << 32 <= pad(c_limit + 1) * 256 * 2
+
+
 def test_library_adam_is_a_torch_adam_and_survives_copies():
     """nerf_shared_amd.optim.Adam keeps torch.optim.Adam's surface (constructor, param_groups, state_dict keys, pickling);
     what its kernel does not cover is refused at construction or at step time, never silently handled elsewhere."""

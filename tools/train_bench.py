@@ -29,7 +29,7 @@ def main():
                     help="amd: nerf_shared_amd.optim.Adam (what utils.get_optimizer returns); foreach / fused: torch.optim.Adam")
     ap.add_argument("--tuning", type=int, default=0, help="nerf_amd_set_tuning(0, value): 50 = round-1 weight-gradient kernel")
     ap.add_argument("--precision", choices=["bf16", "fp32_split", "fp32"], default="bf16",
-                    help="arithmetic of the field and of its backward pass (fp32 trains on the split-precision kernels)")
+                    help="arithmetic of the field and of its backward pass (fp32 trains on the exact-fp32 path, csrc/train_f32.hip)")
     ap.add_argument("--netdepth", type=int, default=8, help="anything but 8 x 256 with skip 4 trains on the exact-fp32 path (csrc/train_f32.hip)")
     ap.add_argument("--netwidth", type=int, default=256)
     ap.add_argument("--skip", type=int, default=4)
