@@ -266,7 +266,7 @@ __global__ __launch_bounds__(64 * RAYS_PER_WG) void composite_bwd_kernel(
         const float m = (q != q) ? q : (q > 1e-10f ? q : 1e-10f);
         const float gq = (q > 1e-10f || q != q) ? -g_disp[r] / (m * m) : 0.0f;   // d(1/max(1e-10, q))/dq
         gdep += gq / sacc;
-        gacc += -gq * sdepth / (sacc * sacc);
+        gacc += -gq * (q / sacc);                       // autograd's div backward: -grad * ((self / other) / other)
     }
     if (white_bkgd) gacc -= gr + gg + gb;
     // ---- sweep 2, last chunk first: suffix sums of u = v w
@@ -275,7 +275,7 @@ __global__ __launch_bounds__(64 * RAYS_PER_WG) void composite_bwd_kernel(
     for (int s0 = ((S - 1) / 64) * 64; s0 >= 0; s0 -= 64) {
         const int s = s0 + lane;
         const bool in = s < S;
-        float v = 0.f, w = 0.f, a = 0.f, T = 0.f, cr = 0.f, cg = 0.f, cb = 0.f, sig = 0.f, dist = 0.f;
+        float v = 0.f, w = 0.f, a = 0.f, T = 0.f, cr = 0.f, cg = 0.f, cb = 0.f, sig = 0.f, dz = 0.f, dist = 0.f;
         if (in) {
             const float *qv = raw + (r * S + s) * raw_ch;
             cr = 1.0f / (1.0f + expf(-qv[0]));
@@ -284,7 +284,8 @@ __global__ __launch_bounds__(64 * RAYS_PER_WG) void composite_bwd_kernel(
             sig = qv[3];
             if (noise) sig = sig + noise[r * S + s];
             const float zc = zr[s];
-            dist = ((s + 1 < S) ? zr[s + 1] - zc : 1e10f) * dnorm;
+            dz = (s + 1 < S) ? zr[s + 1] - zc : 1e10f;
+            dist = dz * dnorm;
             a = sa[s]; T = sT[s]; w = sw[s];
             v = gr * cr + gg * cg + gb * cb + gacc + gdep * zc;
             if (g_weights) v += g_weights[r * S + s];
@@ -298,10 +299,15 @@ __global__ __launch_bounds__(64 * RAYS_PER_WG) void composite_bwd_kernel(
             o[1] = gg * w * cg * (1.0f - cg);
             o[2] = gb * w * cb * (1.0f - cb);
             const float oma = 1.0f - a;
-            const float core = (sig > 0.0f && S > 1) ? oma * (v * T - (float)later / (oma + 1e-10f)) : 0.0f;   // dL/dalpha * (1 - alpha)
-            o[3] = dist * core;
+            // dalpha/d(sigma dist) = exp(-sigma dist), evaluated as the forward does, not as 1 - alpha: that difference has
+            // no relative precision left as alpha -> 1, and is exactly 0 where alpha rounds to 1 and the reference's is not.
+            const float e = expf(-fmaxf(sig, 0.0f) * dist);
+            const float core = S > 1 ? e * (v * T - (float)later / (oma + 1e-10f)) : 0.0f;   // dL/dalpha * exp(-sigma dist)
+            o[3] = sig > 0.0f ? dist * core : 0.0f;              // relu's backward: exactly 0 at sigma <= 0, whatever comes down
             for (int c = 4; c < raw_ch; ++c) o[c] = 0.0f;
-            gdn += core * sig * (dist / dnorm);                  // dL/ddist * dz
+            // dL/ddist * dz.  The factor is relu(sigma), not a mask: autograd's mul backward gives NaN * 0 = NaN on a ray whose
+            // upstream gradient is NaN (disp of an empty ray), so dL/d|rays_d| is NaN there as in the reference.
+            gdn += core * fmaxf(sig, 0.0f) * dz;
         }
     }
     if (g_rays_d) {

@@ -597,7 +597,8 @@ class Renderer(torch.nn.Module):
     def raw2outputs(self, raw, z_vals, rays_d, pytest=False):
         """raw [R,S,>=4], z_vals [R,S], rays_d [R,3] -> rgb_map, disp_map, acc_map,
         weights, depth_map (render_utils.py:241-290).  Differentiable with respect to
-        ``raw`` (HIP backward kernel); z_vals and rays_d are constants."""
+        ``raw`` and ``rays_d`` (HIP backward kernel: the intervals scale with |rays_d|);
+        z_vals are constants."""
         _lib.require_device(raw, "raw")
         dev = raw.device
         raw_c = raw.detach().contiguous().float()

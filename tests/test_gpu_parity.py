@@ -854,6 +854,9 @@ def test_sample_counts_beyond_the_lds_are_refused_with_the_real_reason(dev):
     torch.cuda.synchronize()
     z = out["z_vals"]
     assert z.shape == (8, 2048) and bool((z[:, 1:] >= z[:, :-1]).all()) and bool(torch.isfinite(out["rgb_map"]).all())
+    # and the opted-in launch computes the oracle's render, stage by stage (exact-fp32 field on the same rays)
+    report("lds_mid", staged_check(dev, dict(BASE, N_samples=1024, N_importance=1024), VD, batch.cpu(), (1, 11, 3.0), False,
+                                   "lds mid 1024+1024", "fp32"))
     r = render_utils.Renderer(**BASE)
     with pytest.raises(NerfAmdError, match="bytes of LDS"):
         utils.sample_pdf(torch.rand(4, 6000, device=dev).sort(-1)[0], torch.rand(4, 5999, device=dev), 16, det=True)
