@@ -224,6 +224,15 @@ int     nerf_amd_field_backward(const nerf_amd_model *m, const float *g_raw /* [
                                 float *g_pts /* [R*S,3] overwritten, pts mode, or NULL */,
                                 float *g_rays /* [R,6] dL/d(o,d), accumulated (pass zeros), rays mode, or NULL */,
                                 float *g_viewdirs /* [R,3] accumulated (pass zeros), or NULL */, int precision, void *stream);
+/* The same backward for FROZEN parameters (pose estimation, demo_est_rel_pose.py:87-98; any caller that differentiates
+ * the inputs only): the dX chain alone -> g_pts / g_rays / g_viewdirs as above, by the launch nerf_amd_field_backward
+ * uses for them (ray gradients accumulate with float atomics in both: equal to rounding, not bit for bit); the
+ * weight-gradient products -- the largest launches of a training step -- are not enqueued and no gradient table is
+ * taken.  All three precisions. */
+int     nerf_amd_field_backward_inputs(const nerf_amd_model *m, const float *g_raw, const float *pts, const float *viewdirs,
+                                       const float *rays, int32_t ray_ch, const float *z_vals, int64_t R, int32_t S,
+                                       void *workspace, int64_t workspace_bytes, float *g_pts, float *g_rays,
+                                       float *g_viewdirs, int precision, void *stream);
 
 /* ------------------------------------------------------------------------
  * a11  utils.sample_pdf                       utils.py:74-117
@@ -331,6 +340,38 @@ int nerf_amd_make_rays(int32_t H, int32_t W, const double *K4, const float *c2w,
  * flat pixels [pix0, pix0+n) -> g_c2w (12 floats, 3x4 row-major, DEVICE, overwritten). */
 int nerf_amd_get_rays_backward(int32_t H, int32_t W, const double *K4, int64_t pix0, int64_t n, const float *g_rays_o,
                                const float *g_rays_d, float *g_c2w, void *stream);
+
+/* ------------------------------------------------------------------------
+ * Pose estimation (examples/relative_pose_estimation_demo/demo_est_rel_pose.py:74-98): the loop optimises seven numbers
+ * behind a camera pose against a few hundred SELECTED pixels.  Everything below reads the pose from DEVICE memory, so
+ * the loop body neither synchronises nor copies to the host and can be captured in a HIP graph.
+ *
+ * get_rays (utils.py:33-42) at n selected pixels: pix [n,2] int32 DEVICE, (x, y) = (column, row) per ray; c2w DEVICE,
+ * rows 0..2 of a camera-to-world matrix, row r at c2w + r * c2w_row_stride floats (4 for a contiguous [3,4] or [4,4]).
+ * rays_o / rays_d [n,3] receive exactly what nerf_amd_make_rays writes for pixel y * W + x (same operations, same
+ * order).  Pixels are not range-checked on the device (they only enter arithmetic, never an address).
+ * ------------------------------------------------------------------------ */
+int nerf_amd_rays_at_pixels(int32_t H, int32_t W, const double *K4 /* HOST {fx, fy, cx, cy} */, const float *c2w,
+                            int32_t c2w_row_stride, const int32_t *pix, int64_t n, float *rays_o, float *rays_d,
+                            void *stream);
+/* Its backward with respect to the pose: g_rays_o / g_rays_d [n,3] (either may be NULL = zero) -> g_c2w, 12 floats
+ * (3x4 row-major, DEVICE, overwritten): g_c2w[k][m] = sum_i g_rays_d[i][k] dir_i[m], g_c2w[k][3] = sum_i g_rays_o[i][k].
+ * Order-fixed: per-thread partial sums, a butterfly reduction inside each wave, the wave sums added in index order; no
+ * float atomics, so equal inputs give equal bits.  n <= 16384 is one launch; beyond that `partials` (256 * 12 floats,
+ * DEVICE) is required and a second tiny launch adds the per-block sums in block order. */
+int nerf_amd_rays_at_pixels_backward(int32_t H, int32_t W, const double *K4, const int32_t *pix, int64_t n,
+                                     const float *g_rays_o, const float *g_rays_d, float *g_c2w, float *partials,
+                                     void *stream);
+
+/* The demo's camera_transf module (demo_est_rel_pose.py:36-66) as one launch each way.  w[3], v[3], theta[1], x[16]
+ * (4x4 row-major) and T[16] are DEVICE fp32:   T = exp_i x,  with K = [w]x (the cross-product matrix of w),
+ *   exp_i[:3,:3] = I + sin(theta) K + (1 - cos(theta)) K^2
+ *   exp_i[:3,3]  = (theta I + (1 - cos(theta)) K + (theta - sin(theta)) K^2) v          exp_i[3,:] = (0, 0, 0, 1)
+ * evaluated in fp64 from the fp32 inputs and rounded once (1 - cos(theta) and theta - sin(theta) cancel in fp32).
+ * _backward: g_T[16] -> g_w[3], g_v[3], g_theta[1] (overwritten) from the analytic derivatives; x is a constant. */
+int nerf_amd_se3_transform(const float *w, const float *v, const float *theta, const float *x, float *T, void *stream);
+int nerf_amd_se3_transform_backward(const float *w, const float *v, const float *theta, const float *x, const float *g_T,
+                                    float *g_w, float *g_v, float *g_theta, void *stream);
 
 /* Image output stage: utils.to8b (utils.py:30) as used by Renderer.render_from_batch_poses
  * (render_utils.py:312): out[i] = uint8(255 * clip(x[i], 0, 1)), truncating; NaN -> 0.

@@ -32,6 +32,8 @@ EXPORTS = (
     "nerf_amd_profile_enable", "nerf_amd_profile_collect", "nerf_amd_set_tuning",
     "nerf_amd_model_supports_training", "nerf_amd_train_workspace", "nerf_amd_field_forward_train",
     "nerf_amd_field_backward", "nerf_amd_coarse_z", "nerf_amd_resample", "nerf_amd_get_rays_backward", "nerf_amd_to8b", "nerf_amd_ndc_rays_backward", "nerf_amd_adam_step", "nerf_amd_adam_step_device", "nerf_amd_img2mse", "nerf_amd_img2mse_backward", "nerf_amd_assemble_rays",
+    "nerf_amd_rays_at_pixels", "nerf_amd_rays_at_pixels_backward", "nerf_amd_se3_transform", "nerf_amd_se3_transform_backward",
+    "nerf_amd_field_backward_inputs",
 )
 
 
@@ -106,6 +108,15 @@ def _load():
                                                  c_void_p, c_void_p, c_int64, c_int, c_void_p]),
         "nerf_amd_field_backward": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_void_p, c_int64, c_int32,
                                             c_void_p, c_int64, pp_f, pp_f, c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p]),
+        "nerf_amd_field_backward_inputs": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_void_p, c_int64, c_int32,
+                                                   c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int, c_void_p]),
+        "nerf_amd_rays_at_pixels": (c_int, [c_int32, c_int32, POINTER(c_double), c_void_p, c_int32, c_void_p, c_int64, c_void_p,
+                                            c_void_p, c_void_p]),
+        "nerf_amd_rays_at_pixels_backward": (c_int, [c_int32, c_int32, POINTER(c_double), c_void_p, c_int64, c_void_p, c_void_p,
+                                                     c_void_p, c_void_p, c_void_p]),
+        "nerf_amd_se3_transform": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+        "nerf_amd_se3_transform_backward": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                                    c_void_p]),
         "nerf_amd_get_rays_backward": (c_int, [c_int32, c_int32, POINTER(c_double), c_int64, c_int64, c_void_p, c_void_p,
                                                c_void_p, c_void_p]),
         "nerf_amd_to8b": (c_int, [c_void_p, c_int64, c_void_p, c_void_p]),

@@ -403,25 +403,27 @@ int nerf_amd_field_forward_train(const nerf_amd_model *m, const float *pts, cons
     return rc ? fail(rc, "training forward launch failed") : NERF_AMD_OK;
 }
 
-int nerf_amd_field_backward(const nerf_amd_model *m, const float *g_raw, const float *pts, const float *viewdirs,
-                            const float *rays, int32_t ray_ch, const float *z_vals, int64_t R, int32_t S,
-                            void *workspace, int64_t workspace_bytes, float *const *grad_weights,
-                            float *const *grad_biases, int n_tensors, float *g_pts, float *g_rays, float *g_viewdirs,
-                            int precision, void *stream) {
+// nerf_amd_field_backward (with_params: dX chain, then the weight-gradient products into grad_weights / grad_biases) and
+// nerf_amd_field_backward_inputs (the dX chain alone; no tables) are one function: the same checks, the same dX launch.
+static int field_backward(const nerf_amd_model *m, const float *g_raw, const float *pts, const float *viewdirs,
+                   const float *rays, int32_t ray_ch, const float *z_vals, int64_t R, int32_t S,
+                   void *workspace, int64_t workspace_bytes, bool with_params, float *const *grad_weights,
+                   float *const *grad_biases, int n_tensors, float *g_pts, float *g_rays, float *g_viewdirs,
+                   int precision, void *stream) {
     const int64_t n_points = R * S;
-    if (!m || R < 0 || S < 1 || !grad_weights || !grad_biases) return fail(NERF_AMD_EINVAL, "bad backward arguments");
+    if (!m || R < 0 || S < 1 || (with_params && (!grad_weights || !grad_biases))) return fail(NERF_AMD_EINVAL, "bad backward arguments");
     const bool vd = m->prog.arch.use_viewdirs != 0;
     if ((!pts && (ray_ch != (vd ? 11 : 8) || !rays || !z_vals)) || (pts && vd && !viewdirs))
         return fail(NERF_AMD_EINVAL, "backward needs the forward's inputs (pts + viewdirs, or rays [R,11] + z_vals; [R,8] without view branch)");
     const int path = train_path(m, precision);
     if (!path) return fail(NERF_AMD_EUNSUPPORTED, TRAIN_COVER);
-    if (n_tensors != (int)m->prog.tensors.size()) return fail(NERF_AMD_EINVAL, "wrong number of gradient tensors");
+    if (with_params && n_tensors != (int)m->prog.tensors.size()) return fail(NERF_AMD_EINVAL, "wrong number of gradient tensors");
     if (n_points == 0) return NERF_AMD_OK;
     if (path == 2) {                                   // exact fp32, any architecture (train_f32.hip)
         if (int rc0 = need_copy(m, NERF_AMD_COPY_FP32_BWD)) return rc0;
         if (!g_raw || !workspace || workspace_bytes < train_f32_workspace_bytes(m->prog, n_points))
             return fail(NERF_AMD_EINVAL, "null pointer or workspace too small");
-        for (int i = 0; i < n_tensors; ++i)
+        for (int i = 0; with_params && i < n_tensors; ++i)
             if (!grad_weights[i] || !grad_biases[i]) return fail(NERF_AMD_EINVAL, "null gradient pointer");
         const Program &p = m->prog;
         MlpArgs a;
@@ -433,7 +435,9 @@ int nerf_amd_field_backward(const nerf_amd_model *m, const float *g_raw, const f
         else { a.rays = rays; a.ray_stride = ray_ch; a.z_vals = z_vals; a.viewdirs = vd ? rays + 8 : nullptr; a.vd_stride = ray_ch; }
         a.g_pts = g_pts; a.g_rays = g_rays; a.g_vd = vd ? g_viewdirs : nullptr;
         a.P = n_points; a.S = S; a.g_raw = g_raw;
-        int rc = launch_train_f32_backward(p, a, m->d_tlayers, m->stream_f32_t, workspace, grad_weights, grad_biases, static_cast<hipStream_t>(stream));
+        // (the dW / db products of this path are launches of their own after the dX chain: without tables they are skipped)
+        int rc = launch_train_f32_backward(p, a, m->d_tlayers, m->stream_f32_t, workspace, with_params ? grad_weights : nullptr,
+                                           with_params ? grad_biases : nullptr, static_cast<hipStream_t>(stream));
         return rc ? fail(rc, "exact-fp32 backward launch failed") : NERF_AMD_OK;
     }
     const bool split = precision == NERF_AMD_PREC_FP32_SPLIT;
@@ -453,8 +457,26 @@ int nerf_amd_field_backward(const nerf_amd_model *m, const float *g_raw, const f
     int rc = split ? launch_mlp_bwd_split(a, ar.multires, ar.multires_views, vd, m->prog.n_frags_bwd_split_used, s)
                    : launch_mlp_bwd_s16(a, ar.multires, ar.multires_views, vd, m->prog.n_frags_bwd_used, s);
     if (rc) return fail(rc, "backward kernel launch failed");
+    if (!with_params) return NERF_AMD_OK;
     rc = train_param_grads(m->prog, n_points, workspace, grad_weights, grad_biases, m->device, s, split, g_raw);
     return rc ? fail(rc, "weight-gradient GEMMs failed") : NERF_AMD_OK;
+}
+
+int nerf_amd_field_backward(const nerf_amd_model *m, const float *g_raw, const float *pts, const float *viewdirs,
+                            const float *rays, int32_t ray_ch, const float *z_vals, int64_t R, int32_t S,
+                            void *workspace, int64_t workspace_bytes, float *const *grad_weights,
+                            float *const *grad_biases, int n_tensors, float *g_pts, float *g_rays, float *g_viewdirs,
+                            int precision, void *stream) {
+    return field_backward(m, g_raw, pts, viewdirs, rays, ray_ch, z_vals, R, S, workspace, workspace_bytes, true, grad_weights,
+                          grad_biases, n_tensors, g_pts, g_rays, g_viewdirs, precision, stream);
+}
+
+int nerf_amd_field_backward_inputs(const nerf_amd_model *m, const float *g_raw, const float *pts, const float *viewdirs,
+                                   const float *rays, int32_t ray_ch, const float *z_vals, int64_t R, int32_t S,
+                                   void *workspace, int64_t workspace_bytes, float *g_pts, float *g_rays, float *g_viewdirs,
+                                   int precision, void *stream) {
+    return field_backward(m, g_raw, pts, viewdirs, rays, ray_ch, z_vals, R, S, workspace, workspace_bytes, false, nullptr,
+                          nullptr, 0, g_pts, g_rays, g_viewdirs, precision, stream);
 }
 
 int nerf_amd_raw2outputs(const float *raw, int32_t raw_ch, const float *z_vals, const float *rays_d,
@@ -980,6 +1002,35 @@ int nerf_amd_to8b(const float *x, int64_t n, uint8_t *out, void *stream) {
         return fail(NERF_AMD_EINVAL, "to8b: x must be 16-byte and out 4-byte aligned");
     int rc = launch_to8b(x, n, out, static_cast<hipStream_t>(stream));
     return rc ? fail(rc, "to8b launch failed") : NERF_AMD_OK;
+}
+
+int nerf_amd_rays_at_pixels(int32_t H, int32_t W, const double *K4, const float *c2w, int32_t c2w_row_stride, const int32_t *pix,
+                            int64_t n, float *rays_o, float *rays_d, void *stream) {
+    if (H < 1 || W < 1 || !K4 || !c2w || c2w_row_stride < 4 || n < 0 || (n > 0 && (!pix || !rays_o || !rays_d)))
+        return fail(NERF_AMD_EINVAL, "bad rays_at_pixels arguments");
+    int rc = launch_rays_at_pixels(K4, c2w, c2w_row_stride, pix, n, rays_o, rays_d, static_cast<hipStream_t>(stream));
+    return rc ? fail(rc, "rays_at_pixels launch failed") : NERF_AMD_OK;
+}
+
+int nerf_amd_rays_at_pixels_backward(int32_t H, int32_t W, const double *K4, const int32_t *pix, int64_t n, const float *g_rays_o,
+                                     const float *g_rays_d, float *g_c2w, float *partials, void *stream) {
+    if (H < 1 || W < 1 || !K4 || n < 0 || (n > 0 && !pix) || !g_c2w) return fail(NERF_AMD_EINVAL, "bad rays_at_pixels_backward arguments");
+    int rc = launch_rays_at_pixels_bwd(K4, pix, n, g_rays_o, g_rays_d, g_c2w, partials, static_cast<hipStream_t>(stream));
+    return rc ? fail(rc, rc == NERF_AMD_EINVAL ? "rays_at_pixels_backward: n > 16384 needs the partials buffer (256 * 12 floats)"
+                                               : "rays_at_pixels_backward launch failed") : NERF_AMD_OK;
+}
+
+int nerf_amd_se3_transform(const float *w, const float *v, const float *theta, const float *x, float *T, void *stream) {
+    if (!w || !v || !theta || !x || !T) return fail(NERF_AMD_EINVAL, "bad se3_transform arguments");
+    int rc = launch_se3_transform(w, v, theta, x, T, static_cast<hipStream_t>(stream));
+    return rc ? fail(rc, "se3_transform launch failed") : NERF_AMD_OK;
+}
+
+int nerf_amd_se3_transform_backward(const float *w, const float *v, const float *theta, const float *x, const float *g_T, float *g_w,
+                                    float *g_v, float *g_theta, void *stream) {
+    if (!w || !v || !theta || !x || !g_T || !g_w || !g_v || !g_theta) return fail(NERF_AMD_EINVAL, "bad se3_transform_backward arguments");
+    int rc = launch_se3_transform_bwd(w, v, theta, x, g_T, g_w, g_v, g_theta, static_cast<hipStream_t>(stream));
+    return rc ? fail(rc, "se3_transform_backward launch failed") : NERF_AMD_OK;
 }
 
 int nerf_amd_make_rays(int32_t H, int32_t W, const double *K4, const float *c2w, const float *c2w_static,

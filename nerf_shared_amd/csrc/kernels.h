@@ -189,5 +189,14 @@ int launch_to8b(const float *x, int64_t n, uint8_t *out, hipStream_t s);
 int launch_make_rays(int H, int W, const double *K4, const float *c2w, const float *c2w_static,
                      int64_t pix0, int64_t n, float near, float far, int use_viewdirs, int ndc,
                      float *rays_out, hipStream_t s);
+// pose estimation (demo_est_rel_pose.py:74-98): rays at selected pixels with the pose in device memory, and the se(3) module
+constexpr int RAYS_AT_BWD_PER_BLOCK = 16384, RAYS_AT_BWD_MAX_BLOCKS = 256;
+int launch_rays_at_pixels(const double *K4, const float *c2w, int c2w_stride, const int32_t *pix, int64_t n, float *rays_o,
+                          float *rays_d, hipStream_t s);
+int launch_rays_at_pixels_bwd(const double *K4, const int32_t *pix, int64_t n, const float *g_o, const float *g_d, float *g_c2w,
+                              float *partials, hipStream_t s);
+int launch_se3_transform(const float *w, const float *v, const float *theta, const float *x, float *T, hipStream_t s);
+int launch_se3_transform_bwd(const float *w, const float *v, const float *theta, const float *x, const float *g_T, float *g_w,
+                             float *g_v, float *g_theta, hipStream_t s);
 
 }  // namespace na

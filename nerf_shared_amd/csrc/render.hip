@@ -887,4 +887,196 @@ int launch_make_rays(int H, int W, const double *K4, const float *c2w, const flo
     return hipGetLastError() == hipSuccess ? NERF_AMD_OK : NERF_AMD_EHIP;
 }
 
+// ---------------------------------------------------------------------------
+// Pose estimation (demo_est_rel_pose.py:74-98): get_rays at selected pixels, the pose read from device memory.
+// ---------------------------------------------------------------------------
+struct PixCam { float fx, fy, cx, cy; };
+
+// make_rays_kernel's arithmetic for pixel (x, y) = pix[idx]: the same operations in the same order, so the result equals
+// get_rays(...)[y, x] bit for bit.  One thread per ray; the 12 pose values are loaded (uniformly) by every thread.
+__global__ __launch_bounds__(256) void rays_at_pixels_kernel(PixCam k, const float *c2w, int stride, const int32_t *pix, int64_t n,
+                                                             float *rays_o, float *rays_d) {
+    const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx >= n) return;
+    float c[12];
+#pragma unroll
+    for (int r = 0; r < 3; ++r)
+#pragma unroll
+        for (int m = 0; m < 4; ++m) c[4 * r + m] = c2w[r * stride + m];
+    const float i = (float)pix[2 * idx], j = (float)pix[2 * idx + 1];
+    const float dx = (i - k.cx) / k.fx, dy = -(j - k.cy) / k.fy, dz = -1.0f;
+    float o[3], d[3];
+    cam_ray(c, dx, dy, dz, o, d);
+    rays_o[3 * idx] = o[0]; rays_o[3 * idx + 1] = o[1]; rays_o[3 * idx + 2] = o[2];
+    rays_d[3 * idx] = d[0]; rays_d[3 * idx + 1] = d[1]; rays_d[3 * idx + 2] = d[2];
+}
+
+int launch_rays_at_pixels(const double *K4, const float *c2w, int c2w_stride, const int32_t *pix, int64_t n, float *rays_o,
+                          float *rays_d, hipStream_t s) {
+    if (n <= 0) return NERF_AMD_OK;
+    const PixCam k = {(float)K4[0], (float)K4[1], (float)K4[2], (float)K4[3]};
+    hipLaunchKernelGGL(rays_at_pixels_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, k, c2w, c2w_stride, pix, n, rays_o, rays_d);
+    return hipGetLastError() == hipSuccess ? NERF_AMD_OK : NERF_AMD_EHIP;
+}
+
+// Backward with respect to the pose (the sums of get_rays_bwd_kernel over the selected pixels), in a FIXED order: every thread
+// adds its rays in index order, a butterfly adds the 64 lanes of a wave (every lane ends with the same bits), thread m < 12
+// adds the 16 wave sums of entry m in wave order; several blocks leave their 12 sums in `partials` for the finish kernel.
+// The loop is grid-strided, so any grid covers any n: RAYS_AT_BWD_PER_BLOCK (kernels.h) only chooses how many blocks are
+// launched (<= RAYS_AT_BWD_MAX_BLOCKS = the rows of `partials`) and need not be a multiple of the block size.
+constexpr int RAP_BLOCK = 1024;
+__global__ __launch_bounds__(RAP_BLOCK) void rays_at_pixels_bwd_kernel(PixCam k, const int32_t *pix, int64_t n, const float *g_o,
+                                                                       const float *g_d, float *g_c2w, float *partials) {
+    __shared__ float part[RAP_BLOCK / 64][12];
+    float acc[12];
+#pragma unroll
+    for (int i = 0; i < 12; ++i) acc[i] = 0.f;
+    const int64_t stride = (int64_t)gridDim.x * RAP_BLOCK;
+    for (int64_t idx = (int64_t)blockIdx.x * RAP_BLOCK + threadIdx.x; idx < n; idx += stride) {
+        const float i = (float)pix[2 * idx], j = (float)pix[2 * idx + 1];
+        const float dir[3] = {(i - k.cx) / k.fx, -(j - k.cy) / k.fy, -1.0f};
+#pragma unroll
+        for (int r = 0; r < 3; ++r) {
+            const float gd = g_d ? g_d[3 * idx + r] : 0.f;
+#pragma unroll
+            for (int m = 0; m < 3; ++m) acc[4 * r + m] += gd * dir[m];
+            if (g_o) acc[4 * r + 3] += g_o[3 * idx + r];
+        }
+    }
+#pragma unroll
+    for (int i = 0; i < 12; ++i) {
+        const float v = wave_sum(acc[i]);
+        if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6][i] = v;
+    }
+    __syncthreads();
+    if (threadIdx.x < 12) {
+        float t = 0.f;
+#pragma unroll
+        for (int w = 0; w < RAP_BLOCK / 64; ++w) t += part[w][threadIdx.x];
+        if (gridDim.x == 1) g_c2w[threadIdx.x] = t;
+        else partials[blockIdx.x * 12 + threadIdx.x] = t;
+    }
+}
+
+__global__ __launch_bounds__(64) void rays_at_pixels_bwd_finish_kernel(const float *partials, int n_parts, float *g_c2w) {
+    if (threadIdx.x >= 12) return;
+    float t = 0.f;
+    for (int b = 0; b < n_parts; ++b) t += partials[b * 12 + threadIdx.x];       // block order: independent of scheduling
+    g_c2w[threadIdx.x] = t;
+}
+
+int launch_rays_at_pixels_bwd(const double *K4, const int32_t *pix, int64_t n, const float *g_o, const float *g_d, float *g_c2w,
+                              float *partials, hipStream_t s) {
+    if (n <= 0) return hipMemsetAsync(g_c2w, 0, 12 * sizeof(float), s) == hipSuccess ? NERF_AMD_OK : NERF_AMD_EHIP;
+    int64_t blocks = (n + RAYS_AT_BWD_PER_BLOCK - 1) / RAYS_AT_BWD_PER_BLOCK;
+    if (blocks > RAYS_AT_BWD_MAX_BLOCKS) blocks = RAYS_AT_BWD_MAX_BLOCKS;
+    if (blocks > 1 && !partials) return NERF_AMD_EINVAL;
+    const PixCam k = {(float)K4[0], (float)K4[1], (float)K4[2], (float)K4[3]};
+    hipLaunchKernelGGL(rays_at_pixels_bwd_kernel, dim3((unsigned)blocks), dim3(RAP_BLOCK), 0, s, k, pix, n, g_o, g_d, g_c2w, partials);
+    if (blocks > 1) hipLaunchKernelGGL(rays_at_pixels_bwd_finish_kernel, dim3(1), dim3(64), 0, s, partials, (int)blocks, g_c2w);
+    return hipGetLastError() == hipSuccess ? NERF_AMD_OK : NERF_AMD_EHIP;
+}
+
+// ---------------------------------------------------------------------------
+// The demo's se(3) module (demo_est_rel_pose.py:36-66): T = exp_i x, with K = [w]x,
+//   exp_i[:3,:3] = I + sin(th) K + (1 - cos(th)) K^2,   exp_i[:3,3] = (th I + (1 - cos(th)) K + (th - sin(th)) K^2) v.
+// Seven parameters and a 4x4: latency is all there is, so ONE lane of one wave does the few hundred operations, in fp64
+// (1 - cos(th) and th - sin(th) cancel in fp32; the seven inputs are fp32, every result is rounded once).  No reduction, no LDS.
+// ---------------------------------------------------------------------------
+struct Se3 {
+    double K[3][3], K2[3][3], s, c, th, c1, c2;      // c1 = 1 - cos(th), c2 = th - sin(th)
+    double v[3];
+};
+
+__device__ __forceinline__ Se3 se3_load(const float *w, const float *v, const float *theta) {
+    Se3 e;
+    const double w0 = w[0], w1 = w[1], w2 = w[2];
+    const double K[3][3] = {{0.0, -w2, w1}, {w2, 0.0, -w0}, {-w1, w0, 0.0}};
+    for (int i = 0; i < 3; ++i)
+        for (int j = 0; j < 3; ++j) {
+            e.K[i][j] = K[i][j];
+            e.K2[i][j] = K[i][0] * K[0][j] + K[i][1] * K[1][j] + K[i][2] * K[2][j];
+        }
+    e.th = theta[0];
+    e.s = sin(e.th); e.c = cos(e.th);
+    // 1 - cos(th) = 2 sin^2(th / 2): no cancellation for small th; th - sin(th) from its series below 1e-2 (next term th^9 / 9!)
+    const double h = sin(0.5 * e.th);
+    e.c1 = 2.0 * h * h;
+    const double t2 = e.th * e.th;
+    e.c2 = fabs(e.th) < 1e-2 ? e.th * t2 * (1.0 / 6.0 - t2 * (1.0 / 120.0 - t2 * (1.0 / 5040.0))) : e.th - e.s;
+    e.v[0] = v[0]; e.v[1] = v[1]; e.v[2] = v[2];
+    return e;
+}
+
+__global__ __launch_bounds__(64) void se3_transform_kernel(const float *w, const float *v, const float *theta, const float *x, float *T) {
+    if (threadIdx.x != 0) return;
+    const Se3 e = se3_load(w, v, theta);
+    double E[4][4];
+    for (int i = 0; i < 3; ++i) {
+        double u = 0.0;
+        for (int j = 0; j < 3; ++j) {
+            const double id = i == j ? 1.0 : 0.0;
+            E[i][j] = id + e.s * e.K[i][j] + e.c1 * e.K2[i][j];
+            u += (e.th * id + e.c1 * e.K[i][j] + e.c2 * e.K2[i][j]) * e.v[j];
+        }
+        E[i][3] = u;
+    }
+    E[3][0] = E[3][1] = E[3][2] = 0.0; E[3][3] = 1.0;
+    for (int i = 0; i < 4; ++i)
+        for (int j = 0; j < 4; ++j) {
+            double t = 0.0;
+            for (int m = 0; m < 4; ++m) t += E[i][m] * (double)x[4 * m + j];
+            T[4 * i + j] = (float)t;
+        }
+}
+
+// dL/d(w, v, theta) from g_T: g_E = g_T x^T (rows 0..2), G_R = g_E[:, :3], g_u = g_E[:, 3], G_A = g_u v^T;
+//   g_v  = A^T g_u
+//   g_th = <G_R, cos K + sin K^2> + <G_A, I + sin K + (1 - cos) K^2>
+//   G_K  = sin G_R + (1 - cos)(G_R K^T + K^T G_R) + (1 - cos) G_A + (th - sin)(G_A K^T + K^T G_A)
+//   g_w  = (G_K[2][1] - G_K[1][2], G_K[0][2] - G_K[2][0], G_K[1][0] - G_K[0][1])
+__global__ __launch_bounds__(64) void se3_transform_bwd_kernel(const float *w, const float *v, const float *theta, const float *x,
+                                                               const float *g_T, float *g_w, float *g_v, float *g_theta) {
+    if (threadIdx.x != 0) return;
+    const Se3 e = se3_load(w, v, theta);
+    double GR[3][3], gu[3], GA[3][3];
+    for (int i = 0; i < 3; ++i)
+        for (int j = 0; j < 4; ++j) {
+            double t = 0.0;
+            for (int m = 0; m < 4; ++m) t += (double)g_T[4 * i + m] * (double)x[4 * j + m];
+            if (j < 3) GR[i][j] = t; else gu[i] = t;
+        }
+    for (int i = 0; i < 3; ++i)
+        for (int j = 0; j < 3; ++j) GA[i][j] = gu[i] * e.v[j];
+    double gv[3] = {0.0, 0.0, 0.0}, gth = 0.0, GK[3][3];
+    for (int i = 0; i < 3; ++i)
+        for (int j = 0; j < 3; ++j) {
+            const double id = i == j ? 1.0 : 0.0;
+            gv[j] += (e.th * id + e.c1 * e.K[i][j] + e.c2 * e.K2[i][j]) * gu[i];
+            gth += GR[i][j] * (e.c * e.K[i][j] + e.s * e.K2[i][j]) + GA[i][j] * (id + e.s * e.K[i][j] + e.c1 * e.K2[i][j]);
+            double rk = 0.0, ak = 0.0;           // (G K^T + K^T G)[i][j] for G = G_R, G_A
+            for (int m = 0; m < 3; ++m) {
+                rk += GR[i][m] * e.K[j][m] + e.K[m][i] * GR[m][j];
+                ak += GA[i][m] * e.K[j][m] + e.K[m][i] * GA[m][j];
+            }
+            GK[i][j] = e.s * GR[i][j] + e.c1 * (rk + GA[i][j]) + e.c2 * ak;
+        }
+    g_w[0] = (float)(GK[2][1] - GK[1][2]);
+    g_w[1] = (float)(GK[0][2] - GK[2][0]);
+    g_w[2] = (float)(GK[1][0] - GK[0][1]);
+    g_v[0] = (float)gv[0]; g_v[1] = (float)gv[1]; g_v[2] = (float)gv[2];
+    g_theta[0] = (float)gth;
+}
+
+int launch_se3_transform(const float *w, const float *v, const float *theta, const float *x, float *T, hipStream_t s) {
+    hipLaunchKernelGGL(se3_transform_kernel, dim3(1), dim3(64), 0, s, w, v, theta, x, T);
+    return hipGetLastError() == hipSuccess ? NERF_AMD_OK : NERF_AMD_EHIP;
+}
+
+int launch_se3_transform_bwd(const float *w, const float *v, const float *theta, const float *x, const float *g_T, float *g_w,
+                             float *g_v, float *g_theta, hipStream_t s) {
+    hipLaunchKernelGGL(se3_transform_bwd_kernel, dim3(1), dim3(64), 0, s, w, v, theta, x, g_T, g_w, g_v, g_theta);
+    return hipGetLastError() == hipSuccess ? NERF_AMD_OK : NERF_AMD_EHIP;
+}
+
 }  // namespace na

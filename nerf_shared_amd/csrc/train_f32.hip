@@ -431,6 +431,7 @@ int launch_train_f32_backward(const Program &p, const MlpArgs &a, const TrainLay
         return hipGetLastError() == hipSuccess ? NERF_AMD_OK : NERF_AMD_EHIP;
     });
     if (rc) return rc;
+    if (!gw || !gb) return NERF_AMD_OK;       // frozen parameters (nerf_amd_field_backward_inputs): the dX chain above is all
     // ---- weight and bias gradients, layer by layer (the slab is re-used: everything is in stream order)
     float *slab = t.ws + (int64_t)p.train_f32_rows * t.Pp;
     const int64_t slice_pts = dw_slice_pts(t.Pp), slices = (t.Pp + slice_pts - 1) / slice_pts;

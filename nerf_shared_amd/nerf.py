@@ -211,31 +211,42 @@ class _FieldTrainFn(torch.autograd.Function):
                                     "taken against the wrong weights; run backward before updating the parameters")
         dev = ws.device
         g = g_raw.contiguous().float()
-        # one zeroed buffer for every gradient (head and ray gradients accumulate with atomics), views per tensor
-        sizes, shapes = model._grad_layout()
-        n = len(shapes)
-        flat = torch.zeros(sizes[-1], device=dev, dtype=torch.float32)
-        base = flat.data_ptr()
-        wp = (ctypes.c_void_p * n)(*[base + 4 * o for o in sizes[0:n]])
-        bp = (ctypes.c_void_p * n)(*[base + 4 * o for o in sizes[n:2 * n]])
         need_pts, need_vd, need_rays = ctx.needs_input_grad[2], ctx.needs_input_grad[3], ctx.needs_input_grad[4]
         g_pts = torch.empty(R * S, 3, device=dev, dtype=torch.float32) if (pts is not None and need_pts) else None
         g_rays6 = torch.zeros(R, 6, device=dev, dtype=torch.float32) if (rays is not None and need_rays) else None
         g_vd = torch.zeros(R, 3, device=dev, dtype=torch.float32) if (model.use_viewdirs and ((pts is not None and need_vd) or g_rays6 is not None)) else None
-        with torch.cuda.device(dev):
-            _lib.check(lib.nerf_amd_field_backward(model._handle, g.data_ptr(), _lib.ptr(pts), _lib.ptr(viewdirs), _lib.ptr(rays),
-                                                   rays.shape[1] if rays is not None else 0, _lib.ptr(z_vals), R, S,
-                                                   ws.data_ptr(), ws.numel(), wp, bp, n, _lib.ptr(g_pts), _lib.ptr(g_rays6),
-                                                   _lib.ptr(g_vd), ctx.prec, _lib.stream_of(dev)), "nerf_amd_field_backward")
+        sizes, shapes = model._grad_layout()
+        n = len(shapes)
+        frozen = not any(ctx.needs_input_grad[8:])
+        if frozen:
+            # no parameter asks for a gradient (pose estimation: frozen fields, the rays carry the gradient): the dX chain
+            # alone -- no weight-gradient launches, no parameter-gradient buffer
+            with torch.cuda.device(dev):
+                _lib.check(lib.nerf_amd_field_backward_inputs(model._handle, g.data_ptr(), _lib.ptr(pts), _lib.ptr(viewdirs), _lib.ptr(rays),
+                                                              rays.shape[1] if rays is not None else 0, _lib.ptr(z_vals), R, S,
+                                                              ws.data_ptr(), ws.numel(), _lib.ptr(g_pts), _lib.ptr(g_rays6),
+                                                              _lib.ptr(g_vd), ctx.prec, _lib.stream_of(dev)), "nerf_amd_field_backward_inputs")
+        else:
+            # one zeroed buffer for every gradient (head and ray gradients accumulate with atomics), views per tensor
+            flat = torch.zeros(sizes[-1], device=dev, dtype=torch.float32)
+            base = flat.data_ptr()
+            wp = (ctypes.c_void_p * n)(*[base + 4 * o for o in sizes[0:n]])
+            bp = (ctypes.c_void_p * n)(*[base + 4 * o for o in sizes[n:2 * n]])
+            with torch.cuda.device(dev):
+                _lib.check(lib.nerf_amd_field_backward(model._handle, g.data_ptr(), _lib.ptr(pts), _lib.ptr(viewdirs), _lib.ptr(rays),
+                                                       rays.shape[1] if rays is not None else 0, _lib.ptr(z_vals), R, S,
+                                                       ws.data_ptr(), ws.numel(), wp, bp, n, _lib.ptr(g_pts), _lib.ptr(g_rays6),
+                                                       _lib.ptr(g_vd), ctx.prec, _lib.stream_of(dev)), "nerf_amd_field_backward")
         ctx.ws = None
         g_rays = None
         if g_rays6 is not None:           # [R, 11] = d/d(o, d, near, far, viewdir); [R, 8] without view branch
             g_rays = torch.cat([g_rays6, torch.zeros(R, 2, device=dev)] + ([g_vd] if g_vd is not None else []), -1)
-        grads = []                        # parameter order of _train_params(): weight, bias per linear
-        parts = flat.split([sh[0] * sh[1] for sh in shapes] + [sh[0] for sh in shapes])
-        for i, shape in enumerate(shapes):
-            grads.append(parts[i].view(shape))
-            grads.append(parts[n + i])
+        grads = [None] * (2 * n)          # parameter order of _train_params(): weight, bias per linear
+        if not frozen:
+            parts = flat.split([sh[0] * sh[1] for sh in shapes] + [sh[0] for sh in shapes])
+            for i, shape in enumerate(shapes):
+                grads[2 * i] = parts[i].view(shape)
+                grads[2 * i + 1] = parts[n + i]
         return (None, None, g_pts, g_vd if (pts is not None and need_vd and g_vd is not None) else None, g_rays, None, None, None) + tuple(grads)
 
 

@@ -68,6 +68,39 @@ class Adam(torch.optim.Adam):
             c["step"] += n
         nerf._after_optimizer_step(self, (), {})
 
+    def snapshot_training_state(self, params):
+        """Copies of `params`, of their moments and of the step counts, for restore_training_state(): what a captured
+        step's constructor takes before its warm-up steps (utils.CapturedTrainStep, utils.CapturedPoseStep)."""
+        with torch.no_grad():
+            snap_p = [p.detach().clone() for p in params]
+            snap_s = {p: {k: (v.detach().clone() if isinstance(v, torch.Tensor) else v) for k, v in self.state[p].items()}
+                      for p in params if len(self.state.get(p, {})) > 0}
+        self._sync_steps()
+        return snap_p, snap_s, {gi: c["step"] for gi, c in self._together.items()}
+
+    def restore_training_state(self, params, snapshot):
+        """Put parameters, moments and step counts (host and device) back to `snapshot`; parameters without state then
+        get zero moments, and gradient tensors are zeroed in place (a capture's gradient tensors stay attached: replays
+        fill them)."""
+        snap_p, snap_s, steps_before = snapshot
+        with torch.no_grad():
+            for p, s0 in zip(params, snap_p):
+                p.copy_(s0)
+            for p in params:
+                st = self.state[p]
+                if p in snap_s:
+                    st["exp_avg"].copy_(snap_s[p]["exp_avg"])
+                    st["exp_avg_sq"].copy_(snap_s[p]["exp_avg_sq"])
+                elif len(st) > 0:
+                    st["exp_avg"].zero_()
+                    st["exp_avg_sq"].zero_()
+                if p.grad is not None:
+                    p.grad.zero_()
+        for gi, c in self._together.items():
+            c["step"] = steps_before.get(gi, int(snap_s[c["params"][0]]["step"]) if c["params"][0] in snap_s else 0)
+            if self._device_scalars is not None:
+                self._device_scalars[gi][0].fill_(c["step"])
+
     # -- torch.optim.Optimizer surface -------------------------------------------
     def __getstate__(self):
         self._sync_steps()                 # copies and pickles carry the state tensors only (torch's own __getstate__)

@@ -150,6 +150,127 @@ def get_rays(H, W, K, c2w):
     return b[:, 0:3].reshape(H, W, 3), b[:, 3:6].reshape(H, W, 3)
 
 
+class _RaysAtPixelsFn(torch.autograd.Function):
+    """get_rays_at with a HIP backward with respect to the pose (nerf_amd_rays_at_pixels_backward); nothing touches the host."""
+
+    @staticmethod
+    def forward(ctx, c2w, pix, H, W, K4):
+        dev, n = c2w.device, pix.shape[0]
+        o, d = torch.empty(n, 3, device=dev, dtype=torch.float32), torch.empty(n, 3, device=dev, dtype=torch.float32)
+        k4 = (ctypes.c_double * 4)(*K4)
+        with torch.cuda.device(dev):
+            _lib.check(lib.nerf_amd_rays_at_pixels(H, W, k4, c2w.data_ptr(), c2w.stride(0), pix.data_ptr(), n, o.data_ptr(),
+                                                   d.data_ptr(), _lib.stream_of(dev)), "nerf_amd_rays_at_pixels")
+        ctx.meta = (H, W, K4, tuple(c2w.shape))
+        ctx.pix = pix
+        return o, d
+
+    @staticmethod
+    def backward(ctx, g_o, g_d):
+        H, W, K4, shape = ctx.meta
+        pix = ctx.pix
+        dev, n = pix.device, pix.shape[0]
+        g_o = None if g_o is None else g_o.contiguous().float()
+        g_d = None if g_d is None else g_d.contiguous().float()
+        # the kernel overwrites the first 12 floats = rows 0..2; row 3 of a [4,4] pose gets no gradient
+        g = torch.zeros(shape, device=dev, dtype=torch.float32) if shape[0] > 3 else torch.empty(shape, device=dev, dtype=torch.float32)
+        partials = torch.empty(256 * 12, device=dev, dtype=torch.float32) if n > 16384 else None
+        k4 = (ctypes.c_double * 4)(*K4)
+        with torch.cuda.device(dev):
+            _lib.check(lib.nerf_amd_rays_at_pixels_backward(H, W, k4, pix.data_ptr(), n, _lib.ptr(g_o), _lib.ptr(g_d), g.data_ptr(),
+                                                            _lib.ptr(partials), _lib.stream_of(dev)), "nerf_amd_rays_at_pixels_backward")
+        return g, None, None, None, None
+
+
+def _device_pixels(pixels, H, W, device):
+    """[n, 2] int32 (x, y) on `device`.  Host pixels (list, array, CPU tensor) are checked against the image; a device
+    tensor is converted there and trusted."""
+    if isinstance(pixels, torch.Tensor) and pixels.is_cuda:
+        if pixels.dim() != 2 or pixels.shape[1] != 2 or pixels.is_floating_point():
+            raise _lib.NerfAmdError("pixels must be an integer tensor [n, 2] of (x, y), got %s %s" % (pixels.dtype, tuple(pixels.shape)))
+        return pixels.to(device=device, dtype=torch.int32).contiguous()
+    host = torch.as_tensor(np.asarray(pixels) if not isinstance(pixels, torch.Tensor) else pixels)
+    if host.dim() != 2 or host.shape[1] != 2 or host.is_floating_point():
+        raise _lib.NerfAmdError("pixels must be integers [n, 2] of (x, y), got %s %s" % (host.dtype, tuple(host.shape)))
+    if host.numel() > 0 and (int(host.min()) < 0 or int(host[:, 0].max()) >= W or int(host[:, 1].max()) >= H):
+        raise _lib.NerfAmdError("pixels outside the %d x %d image (x in [0, %d), y in [0, %d))" % (H, W, W, H))
+    return host.to(device=device, dtype=torch.int32).contiguous()
+
+
+def get_rays_at(H, W, K, c2w, pixels):
+    """rays_o, rays_d [n, 3] of the n pixels `pixels` [n, 2] = (x, y) -- column, row, as the pose-estimation demo's
+    `batch` has them (demo_est_rel_pose.py:77-85): get_rays(H, W, K, c2w)[y, x] bit for bit, without generating the other
+    H W - n rays.  c2w is a DEVICE tensor [3, 4] or [4, 4] and is read on the device: no host copy, no synchronisation, so
+    the call can be captured in a HIP graph and sees the pose's current values on every replay (get_rays brings the pose
+    to the host).  Differentiable with respect to c2w; the backward sums in a fixed order (equal inputs, equal bits).
+
+    `pixels`: an integer device tensor (int32, or int64 converted on the device), or host integers (list, array, CPU
+    tensor).  Host pixels outside the image raise NerfAmdError.  A DEVICE tensor is TRUSTED: checking it would need a
+    synchronisation.  (Out-of-range values are harmless to memory -- a pixel only enters arithmetic -- and give the ray
+    of that off-image position.)"""
+    if not (isinstance(c2w, torch.Tensor) and c2w.is_cuda):
+        raise _lib.NerfAmdError("get_rays_at reads the pose on the device: c2w must be a ROCm tensor (utils.get_rays takes host poses)")
+    if c2w.dim() != 2 or c2w.shape[0] not in (3, 4) or c2w.shape[1] != 4:
+        raise _lib.NerfAmdError("c2w must be [3, 4] or [4, 4], got %s" % (tuple(c2w.shape),))
+    pose = c2w if (c2w.dtype == torch.float32 and c2w.stride(1) == 1 and c2w.stride(0) >= 4) else c2w.float().contiguous()
+    pix = _device_pixels(pixels, int(H), int(W), pose.device)
+    K4 = (float(K[0][0]), float(K[1][1]), float(K[0][2]), float(K[1][2]))
+    if not (pose.requires_grad and torch.is_grad_enabled()):
+        pose = pose.detach()
+    return _RaysAtPixelsFn.apply(pose, pix, int(H), int(W), K4)
+
+
+class _Se3Fn(torch.autograd.Function):
+    """T = exp_i(w, v, theta) x (nerf_amd_se3_transform): one launch forward, one backward; x is a constant."""
+
+    @staticmethod
+    def forward(ctx, w, v, theta, x):
+        T = torch.empty(4, 4, device=x.device, dtype=torch.float32)
+        with torch.cuda.device(x.device):
+            _lib.check(lib.nerf_amd_se3_transform(w.data_ptr(), v.data_ptr(), theta.data_ptr(), x.data_ptr(), T.data_ptr(),
+                                                  _lib.stream_of(x.device)), "nerf_amd_se3_transform")
+        ctx.save_for_backward(w, v, theta, x)
+        return T
+
+    @staticmethod
+    def backward(ctx, g_T):
+        w, v, theta, x = ctx.saved_tensors
+        g = torch.empty(7, device=x.device, dtype=torch.float32)
+        g_T = g_T.contiguous().float()
+        with torch.cuda.device(x.device):
+            _lib.check(lib.nerf_amd_se3_transform_backward(w.data_ptr(), v.data_ptr(), theta.data_ptr(), x.data_ptr(), g_T.data_ptr(),
+                                                           g.data_ptr(), g.data_ptr() + 12, g.data_ptr() + 24,
+                                                           _lib.stream_of(x.device)), "nerf_amd_se3_transform_backward")
+        return g[0:3], g[3:6], g[6].reshape(theta.shape), None
+
+
+class CameraTransf(torch.nn.Module):
+    """The pose-estimation demo's camera_transf module (demo_est_rel_pose.py:36-66): a learnable rigid motion
+    exp_i(w, v, theta) applied to a start pose, T = exp_i @ x, with K = [w]x (the cross-product matrix of w):
+
+        exp_i[:3, :3] = I + sin(theta) K + (1 - cos(theta)) K^2
+        exp_i[:3, 3]  = (theta I + (1 - cos(theta)) K + (theta - sin(theta)) K^2) v            exp_i[3] = (0, 0, 0, 1)
+
+    Same parameters (w [3], v [3], theta [], normal(0, 1e-6)), same state_dict; forward and backward are one kernel each
+    (about forty scalar torch ops each way in the demo) and read everything from device memory.  x [4, 4] is a constant:
+    it gets no gradient."""
+
+    def __init__(self):
+        super().__init__()
+        self.w = torch.nn.Parameter(torch.normal(0., 1e-6, size=(3,)))
+        self.v = torch.nn.Parameter(torch.normal(0., 1e-6, size=(3,)))
+        self.theta = torch.nn.Parameter(torch.normal(0., 1e-6, size=()))
+
+    def forward(self, x):
+        _lib.require_device(x, "x")
+        _lib.require_device(self.w, "CameraTransf's parameters")
+        if tuple(x.shape) != (4, 4):
+            raise _lib.NerfAmdError("CameraTransf takes a [4, 4] pose, got %s" % (tuple(x.shape),))
+        if any(p.dtype != torch.float32 or p.device != x.device for p in (self.w, self.v, self.theta)):
+            raise _lib.NerfAmdError("CameraTransf's parameters must be fp32 on the pose's device (%s)" % x.device)
+        return _Se3Fn.apply(self.w, self.v, self.theta, x.detach().float().contiguous())
+
+
 def get_rays_np(H, W, K, c2w):
     """numpy twin used by the reference's training-data batching (utils.py:45-52)."""
     i, j = np.meshgrid(np.arange(W, dtype=np.float32), np.arange(H, dtype=np.float32), indexing='xy')
@@ -281,6 +402,30 @@ def get_optimizer(coarse_model, fine_model, args):
     return torch.optim.Adam(params=params, lr=args.lrate, betas=(0.9, 0.999))
 
 
+def _capture_step(body, optimizer, params, repack_models, dev, warmup):
+    """Warm `body` up on a side stream, capture it in a HIP graph, and put the training state back: constructing a captured
+    step must not train.  The warm-up steps (which the capture needs -- lazy allocations, the optimizer's per-group fast
+    path) run on the caller's placeholder inputs; parameters, moments and step counts are restored afterwards.
+    `repack_models`: models whose parameters the step updates (the re-pack belongs inside the captured step)."""
+    snapshot = optimizer.snapshot_training_state(params)
+    side = torch.cuda.Stream(dev)
+    side.wait_stream(torch.cuda.current_stream(dev))
+    with torch.cuda.stream(side):
+        for i in range(max(1, warmup)):          # (the first step also establishes the optimizer's per-group fast path)
+            body()
+            if i == 0:
+                optimizer.enable_device_scalars()
+    torch.cuda.current_stream(dev).wait_stream(side)
+    for m in repack_models:
+        if m is not None:
+            m.weights_changed()                   # the re-pack of the parameters belongs inside the captured step
+    graph = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(graph):
+        body()
+    optimizer.restore_training_state(params, snapshot)
+    return graph
+
+
 class CapturedTrainStep:
     """One iteration of the reference's training loop (main.py:77-104: render_from_rays -> img2mse(rgb) [+ img2mse(rgb0)]
     -> loss.backward() -> optimizer.step()) captured once in a HIP graph and replayed.
@@ -322,45 +467,7 @@ class CapturedTrainStep:
         self.params = [p for g in optimizer.param_groups for p in g["params"]]
         self.loss = self.psnr = None
         self._lr = None
-        # Constructing the object must not train: the warm-up steps (which the capture needs -- lazy allocations, the
-        # optimizer's per-group fast path) run on the placeholder batch, and parameters, moments and step counts are put
-        # back afterwards.
-        with torch.no_grad():
-            snap_p = [p.detach().clone() for p in self.params]
-            snap_s = {p: {k: (v.detach().clone() if isinstance(v, torch.Tensor) else v) for k, v in optimizer.state[p].items()}
-                      for p in self.params if len(optimizer.state.get(p, {})) > 0}
-        optimizer._sync_steps()
-        steps_before = {gi: c["step"] for gi, c in optimizer._together.items()}
-        side = torch.cuda.Stream(dev)
-        side.wait_stream(torch.cuda.current_stream(dev))
-        with torch.cuda.stream(side):
-            for i in range(max(1, warmup)):          # (the first step also establishes the optimizer's per-group fast path)
-                self._body()
-                if i == 0:
-                    optimizer.enable_device_scalars()
-        torch.cuda.current_stream(dev).wait_stream(side)
-        for m in self.models:
-            if m is not None:
-                m.weights_changed()                   # the re-pack of the parameters belongs inside the captured step
-        self.graph = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(self.graph):
-            self._body()
-        with torch.no_grad():
-            for p, s0 in zip(self.params, snap_p):
-                p.copy_(s0)
-            for p in self.params:
-                st = optimizer.state[p]
-                if p in snap_s:
-                    st["exp_avg"].copy_(snap_s[p]["exp_avg"])
-                    st["exp_avg_sq"].copy_(snap_s[p]["exp_avg_sq"])
-                elif len(st) > 0:
-                    st["exp_avg"].zero_()
-                    st["exp_avg_sq"].zero_()
-                if p.grad is not None:
-                    p.grad.zero_()                    # (the capture's gradient tensors stay attached: replays fill them)
-        for gi, c in optimizer._together.items():
-            c["step"] = steps_before.get(gi, int(snap_s[c["params"][0]]["step"]) if c["params"][0] in snap_s else 0)
-            optimizer._device_scalars[gi][0].fill_(c["step"])
+        self.graph = _capture_step(self._body, optimizer, self.params, self.models, dev, warmup)
 
     def _body(self):
         H, W, K, chunk = self.args
@@ -378,6 +485,94 @@ class CapturedTrainStep:
 
     def __call__(self, rays, target):
         self.rays.copy_(rays if isinstance(rays, torch.Tensor) else torch.stack(list(rays), 0), non_blocking=True)
+        self.target.copy_(target, non_blocking=True)
+        lr = tuple(float(g["lr"]) for g in self.optimizer.param_groups)
+        if lr != self._lr:
+            self.optimizer.sync_lr()
+            self._lr = lr
+        self.graph.replay()
+        self.optimizer.note_replayed_step()
+        return self.loss
+
+
+class CapturedPoseStep:
+    """One iteration of the pose-estimation demo's loop (demo_est_rel_pose.py:74-98) captured once in a HIP graph and replayed:
+
+        pose = cam_transf(start_pose) -> get_rays_at(H, W, K, pose, pixels) -> render_from_rays -> img2mse(rgb, target)
+        -> loss.backward() -> optimizer.step()
+
+    with frozen fields and the seven numbers of a utils.CameraTransf as the only parameters.  Nothing in the body touches
+    the host: the pose goes from the se(3) kernel to the ray kernel in device memory, the fields' backward is the
+    inputs-only one (no weight-gradient launches), and the optimizer reads its step count and learning rate on the device.
+    Between replays, as in CapturedTrainStep:
+      * pixels [n_rays, 2] = (x, y) and target [n_rays, 3] are copied into the capture's input buffers on every call (device
+        or host tensors; device pixels are trusted, see get_rays_at);
+      * change optimizer.param_groups[i]['lr'] (the demo's lrate * 0.8 ** ((k + 1) / 100)) and the next call picks it up;
+      * random draws (perturb, raw_noise_std) advance with every replay;
+      * gradients of the seven parameters are left in `.grad` after every call.
+    `step.pose` is the [4, 4] pose AFTER the last replay's update (cam_transf(start_pose) on the stepped parameters, what
+    the demo prints and compares), a device tensor that the next replay overwrites.  Needs nerf_shared_amd.optim.Adam over
+    cam_transf.parameters() and frozen models (requires_grad_(False)): a field that asked for parameter gradients would
+    take the training backward for gradients nobody steps.  Constructing it leaves the seven parameters, the moments and
+    the step count as they were.
+
+        cam = utils.CameraTransf().to(device)
+        opt = optim.Adam(cam.parameters(), lr=lrate, betas=(0.9, 0.999))
+        step = utils.CapturedPoseStep(renderer, H, W, K, chunk, coarse, fine, cam, start_pose, opt, n_rays)
+        for k in range(n_iters):
+            loss = step(pixels_k, target_k)                      # device scalar
+            for g in opt.param_groups: g['lr'] = lrate * 0.8 ** ((k + 1) / 100)
+    """
+
+    def __init__(self, renderer, H, W, K, chunk, coarse_model, fine_model, cam_transf, start_pose, optimizer, n_rays, warmup=3):
+        from . import optim
+        if not isinstance(optimizer, optim.Adam):
+            raise _lib.NerfAmdError("CapturedPoseStep needs nerf_shared_amd.optim.Adam over cam_transf.parameters(): torch's "
+                                    "optimizers pass step-dependent scalars as kernel arguments, which a graph would freeze")
+        for name, m in (("coarse_model", coarse_model), ("fine_model", fine_model)):
+            if m is not None and any(p.requires_grad for p in m.parameters()):
+                raise _lib.NerfAmdError("CapturedPoseStep optimises the pose against FROZEN fields: call %s.requires_grad_(False) "
+                                        "(its parameters ask for gradients that this step would compute and nobody would use)" % name)
+        self.params = [p for g in optimizer.param_groups for p in g["params"]]
+        mine = {id(p) for p in cam_transf.parameters()}
+        if not self.params or {id(p) for p in self.params} != mine:
+            raise _lib.NerfAmdError("CapturedPoseStep: the optimizer must hold exactly cam_transf's parameters (w, v, theta)")
+        dev = self.params[0].device
+        _lib.require_device(self.params[0], "cam_transf's parameters")
+        self.renderer, self.models, self.cam_transf, self.optimizer = renderer, (coarse_model, fine_model), cam_transf, optimizer
+        self.args = (int(H), int(W), K, chunk)
+        self.start_pose = torch.as_tensor(start_pose, dtype=torch.float32).to(dev).contiguous().clone()
+        if tuple(self.start_pose.shape) != (4, 4):
+            raise _lib.NerfAmdError("start_pose must be [4, 4], got %s" % (tuple(self.start_pose.shape),))
+        # a valid placeholder batch for the warm-up: pixel (0, 0) n_rays times, a grey target
+        self.pixels = torch.zeros(n_rays, 2, device=dev, dtype=torch.int32)
+        self.target = torch.full((n_rays, 3), 0.5, device=dev)
+        self.loss = self.pose = None
+        self._lr = None
+        self.graph = _capture_step(self._body, optimizer, self.params, (), dev, warmup)
+        with torch.no_grad():
+            self.pose.copy_(cam_transf(self.start_pose))          # (the capture left the pose of its own last update there)
+
+    def _body(self):
+        H, W, K, chunk = self.args
+        coarse, fine = self.models
+        for p in self.params:
+            p.grad = None
+        pose = self.cam_transf(self.start_pose)
+        rays_o, rays_d = get_rays_at(H, W, K, pose, self.pixels)
+        rgb, disp, acc, extras = self.renderer.render_from_rays(H, W, K, chunk, torch.stack([rays_o, rays_d], 0), coarse, fine,
+                                                                retraw=True)
+        loss = img2mse(rgb, self.target)          # the demo's loss is the fine pass alone (demo_est_rel_pose.py:92)
+        loss.backward()
+        self.optimizer.step()
+        self.loss = loss.detach()
+        with torch.no_grad():
+            self.pose = self.cam_transf(self.start_pose)
+
+    def __call__(self, pixels, target):
+        H, W = self.args[0], self.args[1]
+        pix = pixels if (isinstance(pixels, torch.Tensor) and pixels.is_cuda) else _device_pixels(pixels, H, W, self.pixels.device)
+        self.pixels.copy_(pix, non_blocking=True)
         self.target.copy_(target, non_blocking=True)
         lr = tuple(float(g["lr"]) for g in self.optimizer.param_groups)
         if lr != self._lr:

@@ -1,0 +1,199 @@
+#!/usr/bin/env python3
+"""Time one iteration of the pose-estimation loop (examples/relative_pose_estimation_demo/demo_est_rel_pose.py:74-98): seven
+pose parameters against `batch` selected pixels of a 400 x 400 view, frozen 8x256 view-branch fields, 64 + 128 samples,
+synthetic weights.  Three legs per (batch, precision):
+
+  a  the loop as it could be written before the device-side ops: the se(3) module in torch ops, utils.get_rays over the whole
+     image (pose through the host), index the selected pixels, render, img2mse, backward with the weight-gradient launches
+     (for this leg the tool sends the inputs-only backward through nerf_amd_field_backward), torch.optim.Adam;
+  b  the device-side ops eagerly: utils.CameraTransf, utils.get_rays_at, inputs-only field backward, optim.Adam;
+  c  utils.CapturedPoseStep: leg b's body captured in a HIP graph, one replay per step.
+
+The synthetic fields get a density bias of +1: at scale 1.0 every sigma is negative and the volume would be empty (a white
+image, no pose gradient); with it the three legs' losses follow the same optimisation and can be compared.
+
+Per leg: host ms per step (wall time of enqueueing the steps, no synchronisation added) and GPU ms per step (events around
+the timed steps).  Prints one JSON line.
+
+    python tools/pose_bench.py [--steps 60] [--warmup 5] [--out profiles/pose_step.json]
+"""
+import argparse
+import contextlib
+import ctypes
+import json
+import os
+import sys
+import time
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+os.environ.setdefault("NERF_AMD_QUIET", "1")
+import numpy as np  # noqa: E402
+import torch  # noqa: E402
+
+from nerf_shared_amd import _lib, nerf, optim, render_utils, synth, utils  # noqa: E402
+
+ARCH = dict(D=8, W=256, output_ch=5, skips=[4], use_viewdirs=True, multires=10, multires_views=4)
+H = W = 400
+LRATE = 0.01
+
+
+class TorchCameraTransf(torch.nn.Module):
+    """The se(3) module of leg a, from the formula in torch ops: exp_i = [[I + sin K + (1 - cos) K^2, A v], [0, 1]] with
+    K = [w]x and A = theta I + (1 - cos) K + (theta - sin) K^2; T = exp_i @ x."""
+
+    def __init__(self):
+        super().__init__()
+        self.w = torch.nn.Parameter(torch.normal(0., 1e-6, size=(3,)))
+        self.v = torch.nn.Parameter(torch.normal(0., 1e-6, size=(3,)))
+        self.theta = torch.nn.Parameter(torch.normal(0., 1e-6, size=()))
+
+    def forward(self, x):
+        w, z = self.w, torch.zeros((), device=self.w.device)
+        K = torch.stack([torch.stack([z, -w[2], w[1]]), torch.stack([w[2], z, -w[0]]), torch.stack([-w[1], w[0], z])])
+        K2, eye = K @ K, torch.eye(3, device=w.device)
+        s, c = torch.sin(self.theta), torch.cos(self.theta)
+        R = eye + s * K + (1 - c) * K2
+        u = (self.theta * eye + (1 - c) * K + (self.theta - s) * K2) @ self.v
+        bottom = torch.tensor([[0., 0., 0., 1.]], device=w.device)
+        return torch.cat([torch.cat([R, u[:, None]], 1), bottom], 0) @ x
+
+
+@contextlib.contextmanager
+def full_backward_for_frozen_models(models):
+    """Leg a only: what a backward through frozen fields cost before nerf_amd_field_backward_inputs existed -- the zeroed
+    parameter-gradient buffer and nerf_amd_field_backward with its weight-gradient launches, for gradients nothing reads.
+    The A/B lives here, in the tool: the binding's inputs-only entry is replaced for the duration of the leg."""
+    by_handle = {m._handle.value: m for m in models}
+    inputs_only = _lib.lib.nerf_amd_field_backward_inputs
+
+    def full(handle, g_raw, pts, viewdirs, rays, ray_ch, z_vals, R, S, ws, ws_bytes, g_pts, g_rays, g_vd, prec, stream):
+        m = by_handle[handle.value]
+        sizes, shapes = m._grad_layout()
+        n = len(shapes)
+        flat = torch.zeros(sizes[-1], device=next(m.parameters()).device, dtype=torch.float32)
+        wp = (ctypes.c_void_p * n)(*[flat.data_ptr() + 4 * o for o in sizes[0:n]])
+        bp = (ctypes.c_void_p * n)(*[flat.data_ptr() + 4 * o for o in sizes[n:2 * n]])
+        return _lib.lib.nerf_amd_field_backward(handle, g_raw, pts, viewdirs, rays, ray_ch, z_vals, R, S, ws, ws_bytes, wp, bp, n,
+                                                g_pts, g_rays, g_vd, prec, stream)
+    _lib.lib.nerf_amd_field_backward_inputs = full
+    try:
+        yield
+    finally:
+        _lib.lib.nerf_amd_field_backward_inputs = inputs_only
+
+
+def timed(step, steps, warmup):
+    for k in range(warmup):
+        step(k)
+    torch.cuda.synchronize()
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    t0 = time.perf_counter()
+    for k in range(steps):
+        loss = step(warmup + k)
+    host = (time.perf_counter() - t0) / steps
+    e1.record()
+    torch.cuda.synchronize()
+    return {"host_ms_per_step": host * 1e3, "gpu_ms_per_step": e0.elapsed_time(e1) / steps, "loss": float(loss.detach())}
+
+
+def run(dev, batch, precision, steps, warmup):
+    models = []
+    for seed in (0, 10):
+        m = nerf.NeRF(**ARCH)
+        m.load_state_dict(synth.torch_state_dict(seed, 1.0, **{**ARCH, "skips": tuple(ARCH["skips"])}))
+        m.precision = precision
+        with torch.no_grad():
+            m.alpha_linear.bias += 1.0            # a fog with structure instead of an empty volume (module docstring)
+        models.append(m.to(dev).requires_grad_(False))
+    r = render_utils.Renderer(perturb=0.0, N_importance=128, N_samples=64, use_viewdirs=True, white_bkgd=True,
+                              raw_noise_std=0.0, near=2.0, far=6.0)
+    K = synth.lego_intrinsics(H, W)
+    start = torch.from_numpy(np.concatenate([synth.LEGO_C2W, np.array([[0, 0, 0, 1]], np.float32)], 0)).to(dev)
+    rng = np.random.default_rng(0)
+    sets = []
+    for _ in range(8):                        # the demo draws a new subset every iteration
+        idx = rng.choice(H * W, size=batch, replace=False)
+        sets.append((torch.from_numpy(np.stack([idx % W, idx // W], -1)).to(dev), torch.rand(batch, 3, device=dev)))
+
+    def decay(opt, k):
+        for g in opt.param_groups:
+            g["lr"] = LRATE * (0.8 ** ((k + 1) / 100))
+
+    out = {}
+    # a: before the device-side ops
+    torch.manual_seed(0)
+    cam_a = TorchCameraTransf().to(dev)
+    opt_a = torch.optim.Adam(cam_a.parameters(), lr=LRATE, betas=(0.9, 0.999))
+
+    def step_a(k):
+        pix, tgt = sets[k % len(sets)]
+        opt_a.zero_grad()
+        pose = cam_a(start)
+        ro, rd = utils.get_rays(H, W, K, pose)
+        rays = torch.stack([ro[pix[:, 1], pix[:, 0]], rd[pix[:, 1], pix[:, 0]]], 0)
+        rgb = r.render_from_rays(H, W, K, 32768, rays, models[0], models[1], retraw=True)[0]
+        loss = utils.img2mse(rgb, tgt)
+        loss.backward()
+        opt_a.step()
+        decay(opt_a, k)
+        return loss
+    for m in models:
+        m._ensure_handle(dev)
+    with full_backward_for_frozen_models(models):
+        out["a_get_rays_then_index"] = timed(step_a, steps, warmup)
+
+    # b: the device-side ops, eagerly
+    torch.manual_seed(0)
+    cam_b = utils.CameraTransf().to(dev)
+    opt_b = optim.Adam(cam_b.parameters(), lr=LRATE, betas=(0.9, 0.999))
+
+    def step_b(k):
+        pix, tgt = sets[k % len(sets)]
+        opt_b.zero_grad()
+        ro, rd = utils.get_rays_at(H, W, K, cam_b(start), pix)
+        rgb = r.render_from_rays(H, W, K, 32768, torch.stack([ro, rd], 0), models[0], models[1], retraw=True)[0]
+        loss = utils.img2mse(rgb, tgt)
+        loss.backward()
+        opt_b.step()
+        decay(opt_b, k)
+        return loss
+    out["b_device_ops_eager"] = timed(step_b, steps, warmup)
+
+    # c: captured
+    torch.manual_seed(0)
+    cam_c = utils.CameraTransf().to(dev)
+    opt_c = optim.Adam(cam_c.parameters(), lr=LRATE, betas=(0.9, 0.999))
+    captured = utils.CapturedPoseStep(r, H, W, K, 32768, models[0], models[1], cam_c, start, opt_c, batch)
+
+    def step_c(k):
+        loss = captured(*sets[k % len(sets)])
+        decay(opt_c, k)
+        return loss
+    out["c_captured_pose_step"] = timed(step_c, steps, warmup)
+    return out
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--steps", type=int, default=60, help="timed steps per leg (>= 50)")
+    ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--batch", type=int, nargs="+", default=[256, 512])          # the demo's --batch_size default is 512
+    ap.add_argument("--precision", nargs="+", default=["bf16", "fp32_split"])
+    ap.add_argument("--out", default=None, help="also write the JSON line to this file")
+    args = ap.parse_args()
+    dev = torch.device("cuda:0")
+    result = {"tool": "pose_bench", "image": [H, W], "samples": [64, 128], "steps": args.steps, "warmup": args.warmup,
+              "device": torch.cuda.get_device_name(0), "runs": []}
+    for precision in args.precision:
+        for batch in args.batch:
+            result["runs"].append({"batch": batch, "precision": precision, **run(dev, batch, precision, args.steps, args.warmup)})
+    line = json.dumps(result)
+    print(line)
+    if args.out:
+        with open(args.out, "w") as f:
+            f.write(line + "\n")
+
+
+if __name__ == "__main__":
+    main()
