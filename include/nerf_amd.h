@@ -235,6 +235,43 @@ int     nerf_amd_field_backward_inputs(const nerf_amd_model *m, const float *g_r
                                        float *g_viewdirs, int precision, void *stream);
 
 /* ------------------------------------------------------------------------
+ * a5  NeRF.get_density                        nerf.py:136-143
+ * The reference evaluates the whole field with an all-ones view direction and keeps channel 3.  sigma depends on the
+ * eight trunk layers and alpha_linear only, so the entry points below take a model WITHOUT view branch: the DENSITY TWIN
+ * of a view-branch model (same pts_linears, output_linear = the model's alpha_linear [1, W]: tensor order 0..D-1
+ * pts_linears.i, D alpha_linear), or an output_linear model itself, whose LAST channel is sigma.  A model with a view
+ * branch is refused with NERF_AMD_EINVAL.  Stale or missing packed copies are refused like everywhere else.
+ *
+ * nerf_amd_density_arch: arch of the density twin of `in` (same trunk and xyz encoding, no view branch, output_ch 1,
+ *   multires_views 0); NERF_AMD_EINVAL for a null pointer or an arch nerf_amd_model_create would refuse.
+ * nerf_amd_density: pts [n,3] -> sigma [n]                             replaces nerf.py:141-143, output[..., -1]
+ *   on the inference kernel of `precision` (its own store when out_ch == 1; with more channels the rows go to
+ *   stream-ordered scratch -- hipMallocAsync on `stream` -- and the last column is copied out).
+ * nerf_amd_density_value_grad: pts [n,3] -> sigma [n] and grad [n,3] = d sigma_i / d pts_i (the gradient of sigma
+ *   itself; a caller's f'(sigma) is one fp32 multiply afterwards).  Replaces autograd.grad(get_density(p).sum(), p)
+ *   on the reference, for frozen parameters.  Two routes, same results class:
+ *     fused    (nerf_amd_density_grad_fused == 1): one launch, no workspace (csrc/density_grad.hip) -- NERF_AMD_PREC_BF16,
+ *              D=8, W=256, skips=[4], multires 10, output_ch <= 16; needs NERF_AMD_COPY_BF16 | NERF_AMD_COPY_BWD;
+ *              bit-equal to the two-launch route (same fragments, same rounding points, no atomics);
+ *     two launches: nerf_amd_field_forward_train + nerf_amd_field_backward_inputs with dL/draw = 1 in the sigma
+ *              column, in `workspace` (nerf_amd_density_grad_workspace bytes, 256-B aligned) -- every model and
+ *              precision nerf_amd_model_supports_training covers, with the packed copies those two calls need.
+ *   The fused kernel runs wherever it covers the model (it is the faster route there);
+ *   nerf_amd_set_tuning(1, 1) sends every call through the two launches (A/B runs, tests).  n = 0 returns NERF_AMD_OK and
+ *   touches nothing.
+ * ------------------------------------------------------------------------ */
+/* arch of the density twin of `in`: same trunk, no view branch, output_ch 1 */
+int     nerf_amd_density_arch(const nerf_amd_arch *in, nerf_amd_arch *out);
+/* m: a model WITHOUT view branch (a density twin, or an output_linear model: sigma = last channel) */
+int     nerf_amd_density(const nerf_amd_model *m, const float *pts, int64_t n, float *sigma /* [n] */,
+                         int precision, void *stream);
+int     nerf_amd_density_grad_fused(const nerf_amd_model *m, int precision);       /* 1: one launch, no workspace */
+int64_t nerf_amd_density_grad_workspace(const nerf_amd_model *m, int64_t n, int precision);   /* 0 when fused */
+int     nerf_amd_density_value_grad(const nerf_amd_model *m, const float *pts, int64_t n, float *sigma /* [n] */,
+                                    float *grad /* [n,3] */, void *workspace, int64_t workspace_bytes,
+                                    int precision, void *stream);
+
+/* ------------------------------------------------------------------------
  * a11  utils.sample_pdf                       utils.py:74-117
  * bins [R,n_bins], weights [R,n_bins-1], u [R,n_samples] or NULL (then
  * u = t_lin[n_samples], the caller's torch.linspace(0,1,n_samples), det=True).
@@ -420,7 +457,8 @@ int nerf_amd_adam_step_device(int32_t n, float *const *params, const float *cons
  * ------------------------------------------------------------------------ */
 int nerf_amd_profile_enable(int on);
 /* Tuning knobs for A/B measurements (results are identical for every setting).
- * key 0: weight-pipeline shape of the fused bf16 kernel (0 = default; see mlp_bf16.hip launch_one). */
+ * key 0: weight-pipeline shape of the fused bf16 kernel (0 = default; see mlp_bf16.hip launch_one).
+ * key 1: route of nerf_amd_density_value_grad (0 = default: the fused kernel where it covers the model, 1 = always two launches). */
 int nerf_amd_set_tuning(int key, int value);
 int nerf_amd_profile_collect(int64_t launches[3], double total_ms[3], double total_points[3]);
 

@@ -34,6 +34,8 @@ EXPORTS = (
     "nerf_amd_field_backward", "nerf_amd_coarse_z", "nerf_amd_resample", "nerf_amd_get_rays_backward", "nerf_amd_to8b", "nerf_amd_ndc_rays_backward", "nerf_amd_adam_step", "nerf_amd_adam_step_device", "nerf_amd_img2mse", "nerf_amd_img2mse_backward", "nerf_amd_assemble_rays",
     "nerf_amd_rays_at_pixels", "nerf_amd_rays_at_pixels_backward", "nerf_amd_se3_transform", "nerf_amd_se3_transform_backward",
     "nerf_amd_field_backward_inputs",
+    "nerf_amd_density_arch", "nerf_amd_density", "nerf_amd_density_grad_fused", "nerf_amd_density_grad_workspace",
+    "nerf_amd_density_value_grad",
 )
 
 
@@ -110,6 +112,11 @@ def _load():
                                             c_void_p, c_int64, pp_f, pp_f, c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p]),
         "nerf_amd_field_backward_inputs": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_void_p, c_int64, c_int32,
                                                    c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int, c_void_p]),
+        "nerf_amd_density_arch": (c_int, [POINTER(Arch), POINTER(Arch)]),
+        "nerf_amd_density": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_int, c_void_p]),
+        "nerf_amd_density_grad_fused": (c_int, [c_void_p, c_int]),
+        "nerf_amd_density_grad_workspace": (c_int64, [c_void_p, c_int64, c_int]),
+        "nerf_amd_density_value_grad": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_void_p]),
         "nerf_amd_rays_at_pixels": (c_int, [c_int32, c_int32, POINTER(c_double), c_void_p, c_int32, c_void_p, c_int64, c_void_p,
                                             c_void_p, c_void_p]),
         "nerf_amd_rays_at_pixels_backward": (c_int, [c_int32, c_int32, POINTER(c_double), c_void_p, c_int64, c_void_p, c_void_p,

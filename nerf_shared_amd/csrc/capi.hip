@@ -1,6 +1,7 @@
 // capi.hip -- the extern "C" boundary declared in include/nerf_amd.h.
 #include <hip/hip_runtime.h>
 
+#include <atomic>
 #include <cmath>
 
 #include <cstdio>
@@ -479,6 +480,126 @@ int nerf_amd_field_backward_inputs(const nerf_amd_model *m, const float *g_raw, 
                           nullptr, 0, g_pts, g_rays, g_viewdirs, precision, stream);
 }
 
+// ---- density queries (NeRF.get_density, nerf.py:136-143): sigma of a model without view branch, and its gradient
+int nerf_amd_density_arch(const nerf_amd_arch *in, nerf_amd_arch *out) {
+    if (!in || !out) return fail(NERF_AMD_EINVAL, "null argument");
+    nerf_amd_arch t = *in;
+    t.use_viewdirs = 0; t.output_ch = 1; t.multires_views = 0;
+    Program p;
+    const char *err = "";
+    if (build_program(t, p, &err) != 0) return fail(NERF_AMD_EINVAL, err);
+    *out = t;
+    return NERF_AMD_OK;
+}
+
+namespace {
+std::atomic<int> g_density_route{0};       // nerf_amd_set_tuning key 1: 0 the fused kernel where it covers the model, 1 always two launches
+const char *NO_VIEW_BRANCH = "density entry points take a model WITHOUT view branch (the density twin of nerf_amd_density_arch, or an output_linear model)";
+
+bool density_fused_covers(const nerf_amd_model *m, int precision) {
+    const nerf_amd_arch &a = m->prog.arch;
+    return precision == NERF_AMD_PREC_BF16 && m->prog.bf16_ok && a.i_embed == 0 && !m->prog.frags_bwd.empty() &&
+           density_grad_fused_supported(a.multires, a.use_viewdirs, m->prog.out_ch);
+}
+bool density_takes_fused(const nerf_amd_model *m, int precision) {
+    // (the fused kernel is the default because it is the faster route wherever it runs: DESIGN.md section 8d)
+    return g_density_route.load(std::memory_order_relaxed) == 0 && density_fused_covers(m, precision);
+}
+// two-launch route: [training workspace | raw [n, out_ch] | dL/draw [n, out_ch]] (the last two only where they are needed:
+// with one channel raw IS sigma)
+struct DensityWs { int64_t train, raw, total; };
+bool density_ws(const nerf_amd_model *m, int64_t n, int precision, DensityWs *w) {
+    const int64_t t = nerf_amd_train_workspace(m, n, precision);
+    if (t < 0) return false;
+    const int och = m->prog.out_ch;
+    w->train = (int64_t)align_up((size_t)t);
+    w->raw = och > 1 ? (int64_t)align_up((size_t)n * och * sizeof(float)) : 0;
+    w->total = w->train + w->raw + (int64_t)align_up((size_t)n * och * sizeof(float));
+    return true;
+}
+}  // namespace
+
+int nerf_amd_density(const nerf_amd_model *m, const float *pts, int64_t n, float *sigma, int precision, void *stream) {
+    if (!m || n < 0) return fail(NERF_AMD_EINVAL, "bad density arguments");
+    if (m->prog.arch.use_viewdirs) return fail(NERF_AMD_EINVAL, NO_VIEW_BRANCH);
+    if (precision != NERF_AMD_PREC_BF16 && precision != NERF_AMD_PREC_FP32_SPLIT && precision != NERF_AMD_PREC_FP32)
+        return fail(NERF_AMD_EINVAL, "unknown precision");
+    if (int rc0 = need_copy(m, precision == NERF_AMD_PREC_BF16 ? NERF_AMD_COPY_BF16 : precision == NERF_AMD_PREC_FP32_SPLIT ? NERF_AMD_COPY_SPLIT : NERF_AMD_COPY_FP32))
+        return rc0;
+    if (n == 0) return NERF_AMD_OK;
+    if (!pts || !sigma) return fail(NERF_AMD_EINVAL, "null pts/sigma");
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const int och = m->prog.out_ch;
+    MlpArgs a;
+    std::memset(&a, 0, sizeof(a));
+    a.pts = pts; a.vd_stride = 3; a.P = n; a.S = 1;
+    if (och == 1) {                 // the field kernel's own store is sigma [n]
+        a.out = sigma;
+        return run_field(m, a, precision, s);
+    }
+    // more channels: the rows go to stream-ordered scratch and the last column is copied out
+    float *raw = nullptr;
+    HIP_TRY(hipMallocAsync(reinterpret_cast<void **>(&raw), (size_t)n * och * sizeof(float), s));
+    a.out = raw;
+    int rc = run_field(m, a, precision, s);
+    if (!rc && (rc = launch_density_last_channel(raw, n, och, sigma, s))) fail(rc, "density channel copy launch failed");
+    (void)hipFreeAsync(raw, s);
+    return rc;
+}
+
+int nerf_amd_density_grad_fused(const nerf_amd_model *m, int precision) {
+    return m && !m->prog.arch.use_viewdirs && density_takes_fused(m, precision) ? 1 : 0;
+}
+
+int64_t nerf_amd_density_grad_workspace(const nerf_amd_model *m, int64_t n, int precision) {
+    if (!m || n < 0 || m->prog.arch.use_viewdirs) return -1;
+    if (density_takes_fused(m, precision)) return 0;
+    DensityWs w;
+    return density_ws(m, n, precision, &w) ? w.total : -1;
+}
+
+int nerf_amd_density_value_grad(const nerf_amd_model *m, const float *pts, int64_t n, float *sigma, float *grad,
+                                void *workspace, int64_t workspace_bytes, int precision, void *stream) {
+    if (!m || n < 0) return fail(NERF_AMD_EINVAL, "bad density_value_grad arguments");
+    if (m->prog.arch.use_viewdirs) return fail(NERF_AMD_EINVAL, NO_VIEW_BRANCH);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const int och = m->prog.out_ch;
+    if (density_takes_fused(m, precision)) {
+        if (int rc0 = need_copy(m, NERF_AMD_COPY_BF16)) return rc0;
+        if (int rc0 = need_copy(m, NERF_AMD_COPY_BWD)) return rc0;
+        if (n == 0) return NERF_AMD_OK;
+        if (!pts || !sigma || !grad) return fail(NERF_AMD_EINVAL, "null pts/sigma/grad");
+        MlpArgs a;
+        std::memset(&a, 0, sizeof(a));
+        a.stream_s16 = m->stream_s16; a.bias_s16 = m->bias_s16; a.stream_bwd = m->stream_bwd;
+        a.pts = pts; a.P = n; a.S = 1; a.out = sigma; a.out_ch = och; a.g_pts = grad;
+        int rc = launch_density_grad(a, m->prog.arch.multires, m->prog.n_frags16_used, (int)m->prog.tiles16.size(), m->prog.n_frags_bwd_used, s);
+        return rc ? fail(rc, "fused density kernel launch failed") : NERF_AMD_OK;
+    }
+    // two launches: the training forward (saves the activations), then the dX chain alone with dL/draw = 1 in the sigma column
+    const int path = train_path(m, precision);
+    if (!path) return fail(NERF_AMD_EUNSUPPORTED, TRAIN_COVER);
+    const int fwd_copy = path == 2 ? NERF_AMD_COPY_FP32 : precision == NERF_AMD_PREC_FP32_SPLIT ? NERF_AMD_COPY_SPLIT : NERF_AMD_COPY_BF16;
+    const int bwd_copy = path == 2 ? NERF_AMD_COPY_FP32_BWD : precision == NERF_AMD_PREC_FP32_SPLIT ? NERF_AMD_COPY_BWD_SPLIT : NERF_AMD_COPY_BWD;
+    if (int rc0 = need_copy(m, fwd_copy)) return rc0;
+    if (int rc0 = need_copy(m, bwd_copy)) return rc0;
+    if (n == 0) return NERF_AMD_OK;
+    if (!pts || !sigma || !grad) return fail(NERF_AMD_EINVAL, "null pts/sigma/grad");
+    DensityWs w;
+    if (!density_ws(m, n, precision, &w)) return fail(NERF_AMD_EUNSUPPORTED, TRAIN_COVER);
+    if (!workspace || workspace_bytes < w.total || (reinterpret_cast<uintptr_t>(workspace) & 255))
+        return fail(NERF_AMD_EINVAL, "workspace missing, misaligned or too small (nerf_amd_density_grad_workspace bytes, 256-B aligned)");
+    char *base = static_cast<char *>(workspace);
+    float *raw = och > 1 ? reinterpret_cast<float *>(base + w.train) : sigma;
+    float *g_raw = reinterpret_cast<float *>(base + w.train + w.raw);
+    int rc = nerf_amd_field_forward_train(m, pts, nullptr, nullptr, 0, nullptr, n, 1, raw, workspace, w.train, precision, stream);
+    if (rc) return rc;
+    if (och > 1 && (rc = launch_density_last_channel(raw, n, och, sigma, s))) return fail(rc, "density channel copy launch failed");
+    if ((rc = launch_density_unit_grad(g_raw, n, och, s))) return fail(rc, "density unit-gradient launch failed");
+    return nerf_amd_field_backward_inputs(m, g_raw, pts, nullptr, nullptr, 0, nullptr, n, 1, workspace, w.train, grad, nullptr, nullptr,
+                                          precision, stream);
+}
+
 int nerf_amd_raw2outputs(const float *raw, int32_t raw_ch, const float *z_vals, const float *rays_d,
                          int32_t rays_d_stride, const float *noise, int64_t R, int32_t S, int white_bkgd,
                          float *rgb_map, float *disp_map, float *acc_map, float *weights, float *depth_map,
@@ -916,6 +1037,7 @@ extern "C" {
 
 int nerf_amd_set_tuning(int key, int value) {
     if (key == 0 && value >= 0 && value <= 115) { g_variant.store(value, std::memory_order_relaxed); return NERF_AMD_OK; }
+    if (key == 1 && value >= 0 && value <= 1) { g_density_route.store(value, std::memory_order_relaxed); return NERF_AMD_OK; }
     return fail(NERF_AMD_EINVAL, "unknown tuning key/value");
 }
 

@@ -116,6 +116,13 @@ int launch_mlp_bf16_s16(const MlpArgs &a, int multires, int multires_views, int 
 int launch_mlp_bf16_s16_save(const MlpArgs &a, int multires, int multires_views, int use_viewdirs, int n_frags_used, int n_tiles, hipStream_t s);
 int launch_mlp_bwd_s16(const MlpArgs &a, int multires, int multires_views, int use_viewdirs, int n_frags_used, hipStream_t s);
 
+// density_grad.hip: sigma [P] (a.out) and d(sigma)/d(point) [P,3] (a.g_pts) of explicit points (a.pts) in one launch, bf16, for
+// the models without view branch of the fused family (a.stream_s16 / a.bias_s16 and a.stream_bwd); sigma = channel out_ch - 1
+bool density_grad_fused_supported(int multires, int use_viewdirs, int out_ch);
+int launch_density_grad(const MlpArgs &a, int multires, int n_frags_fwd, int n_tiles, int n_frags_bwd, hipStream_t s);
+int launch_density_last_channel(const float *raw, int64_t n, int out_ch, float *sigma, hipStream_t s);     // sigma[i] = raw[i, out_ch - 1]
+int launch_density_unit_grad(float *g_raw, int64_t n, int out_ch, hipStream_t s);                          // 1 in the last channel, else 0
+
 // backward.hip
 // split: the arrays of NERF_AMD_PREC_FP32_SPLIT training (hi and lo planes, loss-scale slots) instead of the bf16 ones
 // train_f32.hip: exact-fp32 training for any architecture (NERF_AMD_PREC_FP32): forward with saves, dX chain, dW / db

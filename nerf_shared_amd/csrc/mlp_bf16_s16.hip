@@ -35,7 +35,11 @@ namespace na {
 // Diagnostic build only (cdna_hip_programming.md section 7, in-kernel stamps): per wave, the shader cycles spent
 // in the three segments of a tile -- [loop top .. first weight block published], [.. last MFMA issued],
 // [.. end-of-tile drain] -- summed over the wave's tiles into a buffer nothing else reads.
+#ifdef NA_DEVICE_TEMPLATES_ONLY
+extern unsigned long long *g_stamp_buf;
+#else
 unsigned long long *g_stamp_buf = nullptr;
+#endif
 #define STAMP(var) const unsigned long long var = __builtin_amdgcn_s_memtime()
 #else
 #define STAMP(var)
@@ -779,6 +783,9 @@ __global__ __launch_bounds__(C::WAVES * 64, 2) void mlp_bf16_s16p_kernel(MlpArgs
     }
 }
 
+// density_grad.hip includes this file for the device templates above (NA_DEVICE_TEMPLATES_ONLY): the launchers and the
+// ticket counters below belong to this translation unit alone.
+#ifndef NA_DEVICE_TEMPLATES_ONLY
 // ---- {ticket, done} pairs of the dynamic deal
 namespace {
 constexpr int TILE_CTR_SLOTS = 1024;
@@ -921,5 +928,7 @@ int launch_mlp_bf16_s16_save(const MlpArgs &a, int multires, int multires_views,
     }
     return NERF_AMD_EUNSUPPORTED;
 }
+
+#endif  // NA_DEVICE_TEMPLATES_ONLY
 
 }  // namespace na

@@ -397,6 +397,7 @@ __global__ __launch_bounds__(C::WAVES * 64, 2) void mlp_bwd_s16_kernel(MlpArgs a
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");           // no LDS-DMA may outlive the workgroup
 }
 
+#ifndef NA_DEVICE_TEMPLATES_ONLY      // (density_grad.hip includes this file for the device templates above)
 template <int LX, int LD, bool VD, bool RAYG>
 static int launch_bwd_as(const MlpArgs &a, int n_frags_used, hipStream_t s) {
     constexpr int KE = gen16_ksteps(LX), KD = VD ? gen16_ksteps(LD) : 1;
@@ -430,5 +431,7 @@ int launch_mlp_bwd_s16(const MlpArgs &a, int multires, int multires_views, int u
     }
     return NERF_AMD_EUNSUPPORTED;
 }
+
+#endif  // NA_DEVICE_TEMPLATES_ONLY
 
 }  // namespace na

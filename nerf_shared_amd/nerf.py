@@ -295,6 +295,40 @@ from torch.optim import optimizer as _torch_optimizer  # noqa: E402
 _torch_optimizer.register_optimizer_step_post_hook(_after_optimizer_step)
 
 
+# Density twins (NeRF.density_model): model -> the NeRF without view branch that evaluates its sigma.  Kept beside the models,
+# not on them: a twin is never a submodule (state_dict keys and parameters() of the model stay the reference's) and never part
+# of a model's __dict__ (pickle and copy.deepcopy do not drag it along; the copy makes its own on first use).  A twin holds
+# the model's Parameters, not the model, so the weak keys can die.  Being NeRFs of their own, twins are in _LIVE_MODELS: the
+# optimizer post-step hook -- and a captured step's note_replayed_step(), which calls it -- marks a twin stale whenever a
+# parameter it shares was stepped.
+_DENSITY_TWINS = weakref.WeakKeyDictionary()
+
+
+class _DeadBranchGradFn(torch.autograd.Function):
+    """sigma of the density twin, tied to the parameters of the model sigma does not depend on (feature_linear,
+    views_linears, rgb_linear): they receive the zero-filled gradients autograd gives them when sigma is taken from the
+    full field (the reference's get_density, nerf.py:136-143), instead of none."""
+
+    @staticmethod
+    def forward(ctx, sigma, *dead):
+        ctx.dead = dead
+        return sigma.view_as(sigma)
+
+    @staticmethod
+    def backward(ctx, g):
+        return (g,) + tuple(torch.zeros_like(p) if need else None for p, need in zip(ctx.dead, ctx.needs_input_grad[1:]))
+
+
+def set_density_grad_route(route):
+    """Which kernels NeRF.density_and_grad runs on (results are equal bit for bit; for A/B measurements and tests):
+    'auto' the one-launch kernel (csrc/density_grad.hip) wherever it covers the model, 'two_launch' always the training
+    forward + the dX chain in a workspace."""
+    routes = {"auto": 0, "two_launch": 1}
+    if route not in routes:
+        raise ValueError("route must be one of %s" % sorted(routes))
+    _lib.check(lib.nerf_amd_set_tuning(1, routes[route]), "nerf_amd_set_tuning")
+
+
 class NeRF(nn.Module):
     """The reference's field model (nerf.py:61-143), same constructor, same
     parameters; ``forward`` runs on the MI355X kernels."""
@@ -337,20 +371,29 @@ class NeRF(nn.Module):
         # copies / pickles never share the library handle: the copy creates its own on first use
         state = self.__dict__.copy()
         state.update(_handle=None, _handle_device=None, _packed_key=None, _finalizer=None)
-        for k in ('_mods_cache', '_grad_layout_cache', '_trainable_kernels'):
+        # (the embedders are closures, which pickle refuses: __setstate__ rebuilds them from multires / i_embed)
+        for k in ('_mods_cache', '_grad_layout_cache', '_trainable_kernels', '_trainable_f32', '_packed_copies', 'embed_fn', 'embeddirs_fn'):
             state.pop(k, None)
         return state
 
     def __setstate__(self, state):
         super().__setstate__(state)
+        if 'embed_fn' not in self.__dict__ and 'embed_fn' not in self._modules:
+            self.embed_fn = get_embedder(self.multires, self.i_embed)[0]
+        if 'embeddirs_fn' not in self.__dict__ and 'embeddirs_fn' not in self._modules:
+            self.embeddirs_fn = get_embedder(self.multires_views, self.i_embed)[0] if self.use_viewdirs else None
         _LIVE_MODELS.add(self)
 
     def weights_changed(self):
         """Force a re-pack of the parameters on the next call (needed only after writing through
         `param.data` or other paths that bypass autograd's version counters and the optimizer's post-step hooks -- a
         replayed graph that steps the optimizer is one: after each replay of a graph captured by hand, call the
-        optimizer's note_replayed_step() (nerf_shared_amd.optim.Adam; utils.CapturedTrainStep does) or this)."""
+        optimizer's note_replayed_step() (nerf_shared_amd.optim.Adam; utils.CapturedTrainStep does) or this).  The density
+        twin (density_model) goes stale with its model."""
         self._packed_key = None
+        twin = _DENSITY_TWINS.get(self)
+        if twin is not None:
+            twin._packed_key = None
 
     # -- device-side packed copy of the parameters --------------------------------
     def _linears(self):
@@ -552,11 +595,78 @@ class NeRF(nn.Module):
                                                  _lib.stream_of(dev)), "nerf_amd_mlp_embedded")
         return out.reshape(list(x.shape[:-1]) + [out_ch])
 
+    def density_model(self):
+        """The model that evaluates this model's sigma: the model itself when it has no view branch (sigma is its last
+        output channel), else its density twin -- NeRF(D, W, output_ch=1, skips, use_viewdirs=False, multires, i_embed)
+        whose pts_linears hold this model's Parameter objects and whose output_linear holds alpha_linear's.  Nothing is
+        copied: optimizer steps, load_state_dict and .to() on the model are seen by the twin; it is made on first use and
+        kept outside the model (not a submodule, not in state_dict, not pickled or deep-copied with it)."""
+        if not self.use_viewdirs:
+            return self
+        mine = list(self.pts_linears) + [self.alpha_linear]
+        twin = _DENSITY_TWINS.get(self)
+        if twin is not None:
+            theirs = list(twin.pts_linears) + [twin.output_linear]
+            if not all(a._parameters[k] is b._parameters[k] for a, b in zip(mine, theirs) for k in ('weight', 'bias')):
+                twin = None                    # someone replaced a Parameter object of the model: a new twin
+        if twin is None:
+            twin = NeRF(D=self.D, W=self.W, output_ch=1, skips=self.skips, use_viewdirs=False, multires=self.multires,
+                        multires_views=0, i_embed=self.i_embed)
+            del twin.views_linears             # dead weight of the reference's constructor: in nobody's parameters()
+            for a, b in zip(mine, list(twin.pts_linears) + [twin.output_linear]):
+                b.weight, b.bias = a.weight, a.bias          # the same Parameter objects
+            _DENSITY_TWINS[self] = twin
+        twin.precision = self.precision
+        return twin
+
     def get_density(self, points, chunk=1024 * 64):
-        """Raw sigma with an all-ones view direction (nerf.py:136-143)."""
-        view_dir = torch.ones_like(points[..., 0, :]) if self.use_viewdirs else None
-        output = self.forward(points, view_dir, chunk)
-        return output[..., -1]
+        """Raw sigma at points [..., 3] -> points.shape[:-1] (nerf.py:136-143; the reference's [..., S, 3] is a subset, [N, 3]
+        works).  Runs on the density twin (density_model): the trunk and alpha_linear only -- the value the full field
+        gives with any view direction, bit for bit, without its view branch.  Differentiable like forward(): gradients
+        reach the points and the shared parameters; parameters sigma does not depend on get zeros."""
+        _lib.require_device(points, "points")
+        if points.dim() < 1 or points.shape[-1] != 3:
+            raise _lib.NerfAmdError("points must be [..., 3], got %s" % (tuple(points.shape),))
+        twin = self.density_model()
+        out = twin.forward(points.reshape(-1, 1, 3), None, chunk)            # [N, 1, 1 | output_ch]
+        sigma = out[..., -1].reshape(points.shape[:-1])
+        if twin is not self and sigma.requires_grad:
+            dead = [p for m in (self.feature_linear, self.views_linears[0], self.rgb_linear) for p in m.parameters() if p.requires_grad]
+            if dead:
+                sigma = _DeadBranchGradFn.apply(sigma, *dead)
+        return sigma
+
+    def density_and_grad(self, points):
+        """(sigma, grad): raw sigma at points [..., 3] -> points.shape[:-1], and d sigma / d point -> points.shape, for frozen
+        parameters: what autograd.grad(get_density(p).sum(), p) returns, without an autograd graph (grad mode and
+        requires_grad are ignored), without a host synchronisation, on the current stream (capturable).  The gradient is
+        that of sigma itself; multiply a caller's f'(sigma) in afterwards.  'bf16' models of the fused family with multires 10
+        run one launch without a workspace (csrc/density_grad.hip); everything else the training forward and the dX chain
+        in a workspace of nerf_amd_density_grad_workspace bytes (set_density_grad_route)."""
+        _lib.require_device(points, "points")
+        if points.dim() < 1 or points.shape[-1] != 3:
+            raise _lib.NerfAmdError("points must be [..., 3], got %s" % (tuple(points.shape),))
+        dev = points.device
+        twin = self.density_model()
+        pts = points.detach().reshape(-1, 3).contiguous().float()
+        n = pts.shape[0]
+        twin._ensure_handle(dev)
+        prec = twin._train_precision()
+        handle = twin._model_handle(dev, _lib.TRAIN_COPIES[prec])
+        sigma = torch.empty(n, device=dev, dtype=torch.float32)
+        grad = torch.empty(n, 3, device=dev, dtype=torch.float32)
+        # (a split-precision training call takes at most _SPLIT_TRAIN_MAX_POINTS points: larger queries go in pieces)
+        step = _SPLIT_TRAIN_MAX_POINTS if prec == _lib.PREC_FP32_SPLIT else max(n, 1)
+        for i0 in range(0, max(n, 1), step):
+            k = min(n, i0 + step) - i0
+            nbytes = lib.nerf_amd_density_grad_workspace(handle, k, prec)
+            if nbytes < 0:
+                raise _lib.NerfAmdError("this architecture has no training kernels in this precision: no density gradient")
+            ws = torch.empty(nbytes, dtype=torch.uint8, device=dev) if nbytes > 0 else None
+            with torch.cuda.device(dev):
+                _lib.check(lib.nerf_amd_density_value_grad(handle, pts[i0:].data_ptr(), k, sigma[i0:].data_ptr(), grad[i0:].data_ptr(),
+                                                           _lib.ptr(ws), nbytes, prec, _lib.stream_of(dev)), "nerf_amd_density_value_grad")
+        return sigma.reshape(points.shape[:-1]), grad.reshape(points.shape)
 
     def load_weights_from_keras(self, weights):
         """The weight list of a Keras NeRF (kernel [in, out], bias per layer, in the order pts_linears, feature,
