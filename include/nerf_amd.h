@@ -410,6 +410,55 @@ int nerf_amd_se3_transform(const float *w, const float *v, const float *theta, c
 int nerf_amd_se3_transform_backward(const float *w, const float *v, const float *theta, const float *x, const float *g_T,
                                     float *g_w, float *g_v, float *g_theta, void *stream);
 
+/* ------------------------------------------------------------------------
+ * Pixel selection for pose estimation (demo_est_rel_pose.py:35-47 and :75-79): where the loop looks.  Integer arithmetic
+ * and plain loads / stores only, so every result below is DEFINED exactly (tests compare for equality).  All launches go
+ * on `stream` and can be captured; nothing synchronises or allocates.
+ *
+ * The per-step draw (np.random.choice(M, n, replace=False), interest_regions[rand_inds], obs_img[y, x] in one launch):
+ * n distinct indices out of [0, M), their pixels [n,2] int32 (x, y) and their colours target [n,3] fp32.
+ *   region NULL:  index i is pixel (i % W, i / W) of the whole image; M must be H * W.
+ *   region [M,2] int32 DEVICE (x, y), every entry inside the image (trusted: it addresses the image).
+ *   image: fp32 DEVICE, pixel (x, y) at image + y * row_stride + x * C floats, C >= 3 (the first three are gathered).
+ * The draw is a keyed bijection of [0, M) evaluated at slots 0..n-1 (distinct by construction, O(1) per thread, no
+ * scratch).  All arithmetic uint32 mod 2^32:
+ *   mix(x):  x ^= x >> 16; x *= 0x7feb352d; x ^= x >> 15; x *= 0x846ca68b; x ^= x >> 16
+ *   b = max(1, ceil(bit_length(M - 1) / 2)),  mask = 2^b - 1
+ *   k_r = mix(mix(seed + 0x9e3779b9 (r + 1)) ^ draw),  r = 0..3,  draw = the low 32 bits of *draw_count
+ *   perm(i): x = i; repeat { L = x >> b; R = x & mask; four times (L, R) = (R, L ^ (mix(R ^ k_r) & mask)); x = (L << b) | R }
+ *            until x < M
+ * (four Feistel rounds on [0, 4^b), walked along the cycle that starts below M; the domain is under 4 M, so under four
+ * rounds on average).  *draw_count (int64, DEVICE) is read by the draw and advanced by one behind it in the stream:
+ * replays of a captured call give draws k, k + 1, ... with no host write.  Draws 2^32 apart repeat.
+ * 1 <= n <= M <= 2^31 - 1. */
+int nerf_amd_draw_pixels(int64_t M, int32_t n, uint32_t seed, int64_t *draw_count, const int32_t *region, int32_t H,
+                         int32_t W, const float *image, int64_t row_stride, int32_t C, int32_t *pixels, float *target,
+                         void *stream);
+
+/* Interest points of a sensor image: the built-in STAND-IN for the demo's find_POI (cv2 SIFT, demo_est_rel_pose.py:151-164),
+ * which is defined here rather than matched: exact integer Harris corners.  image uint8 [H,W,C] DEVICE, C = 3 or 4.
+ *   gray = (4899 R + 9617 G + 1868 B + 8192) >> 14;  3x3 Sobel gx, gy at clamped coordinates;
+ *   Sxx, Syy, Sxy = sums of gx^2, gy^2, gx gy over the 5x5 window at clamped coordinates;
+ *   Rsp = 25 (Sxx Syy - Sxy^2) - (Sxx + Syy)^2 in int64 (k = 0.04; every term below 1.8e16).
+ * mask[y,x] (uint8 [H,W] DEVICE) = 1 where Rsp > 0, 100 Rsp >= quality max(Rsp) (quality: integer percent, 1..100), and
+ * Rsp is greater than its 3x3 neighbours earlier in row-major order and >= those later (off-image neighbours do not
+ * count); 0 elsewhere.  The maximum is an integer atomic max: deterministic.
+ * workspace: DEVICE, 8-byte aligned, nerf_amd_interest_points_workspace(H, W) bytes. */
+int64_t nerf_amd_interest_points_workspace(int32_t H, int32_t W);
+int nerf_amd_interest_points(const uint8_t *image, int32_t H, int32_t W, int32_t C, int32_t quality, void *workspace,
+                             uint8_t *mask, void *stream);
+
+/* cv2.dilate(mask, ones((k, k)), iterations=I) by its documented definition (demo_est_rel_pose.py:45): one iteration is
+ * out[y,x] = max over dy, dx in [-a, k - 1 - a], a = k / 2, of in[y + dy, x + dx], off-image pixels ignored; the result
+ * equals I successive iterations (also for even k, whose window is off-centre).  in / out uint8 [H,W] DEVICE, distinct. */
+int nerf_amd_dilate_mask(const uint8_t *in, int32_t H, int32_t W, int32_t k, int32_t iterations, uint8_t *out, void *stream);
+
+/* coords[mask] (demo_est_rel_pose.py:39-47): the (x, y) of the non-zero pixels of mask (uint8 [H,W] DEVICE) in row-major
+ * order -> list [*count, 2] int32 DEVICE (room for H * W entries), *count int64 DEVICE.  Stable: counts per 256 pixels,
+ * a scan, then each pixel written at its rank; no atomics.  block_counts: (H * W + 255) / 256 int32 of DEVICE scratch. */
+int nerf_amd_compact_mask(const uint8_t *mask, int32_t H, int32_t W, int32_t *block_counts, int32_t *list, int64_t *count,
+                          void *stream);
+
 /* Image output stage: utils.to8b (utils.py:30) as used by Renderer.render_from_batch_poses
  * (render_utils.py:312): out[i] = uint8(255 * clip(x[i], 0, 1)), truncating; NaN -> 0.
  * x [n] fp32 DEVICE (16-byte aligned), out [n] uint8 DEVICE (4-byte aligned). */

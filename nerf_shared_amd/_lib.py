@@ -7,7 +7,7 @@ point refuses non-ROCm tensors.
 """
 import ctypes
 import os
-from ctypes import POINTER, Structure, c_char_p, c_double, c_float, c_int, c_int32, c_int64, c_uint16, c_void_p
+from ctypes import POINTER, Structure, c_char_p, c_double, c_float, c_int, c_int32, c_int64, c_uint16, c_uint32, c_void_p
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # NERF_AMD_LIB selects another build of the same library (diagnostic builds such as -DNERF_AMD_STAMPS)
@@ -36,6 +36,8 @@ EXPORTS = (
     "nerf_amd_field_backward_inputs",
     "nerf_amd_density_arch", "nerf_amd_density", "nerf_amd_density_grad_fused", "nerf_amd_density_grad_workspace",
     "nerf_amd_density_value_grad",
+    "nerf_amd_draw_pixels", "nerf_amd_interest_points_workspace", "nerf_amd_interest_points", "nerf_amd_dilate_mask",
+    "nerf_amd_compact_mask",
 )
 
 
@@ -124,6 +126,12 @@ def _load():
         "nerf_amd_se3_transform": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
         "nerf_amd_se3_transform_backward": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                                     c_void_p]),
+        "nerf_amd_draw_pixels": (c_int, [c_int64, c_int32, c_uint32, c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_int64, c_int32,
+                                         c_void_p, c_void_p, c_void_p]),
+        "nerf_amd_interest_points_workspace": (c_int64, [c_int32, c_int32]),
+        "nerf_amd_interest_points": (c_int, [c_void_p, c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p]),
+        "nerf_amd_dilate_mask": (c_int, [c_void_p, c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p]),
+        "nerf_amd_compact_mask": (c_int, [c_void_p, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p]),
         "nerf_amd_get_rays_backward": (c_int, [c_int32, c_int32, POINTER(c_double), c_int64, c_int64, c_void_p, c_void_p,
                                                c_void_p, c_void_p]),
         "nerf_amd_to8b": (c_int, [c_void_p, c_int64, c_void_p, c_void_p]),

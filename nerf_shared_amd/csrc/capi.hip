@@ -1155,6 +1155,45 @@ int nerf_amd_se3_transform_backward(const float *w, const float *v, const float 
     return rc ? fail(rc, "se3_transform_backward launch failed") : NERF_AMD_OK;
 }
 
+int nerf_amd_draw_pixels(int64_t M, int32_t n, uint32_t seed, int64_t *draw_count, const int32_t *region, int32_t H, int32_t W,
+                         const float *image, int64_t row_stride, int32_t C, int32_t *pixels, float *target, void *stream) {
+    if (H < 1 || W < 1 || C < 3 || row_stride < (int64_t)W * C || !draw_count || !image || !pixels || !target)
+        return fail(NERF_AMD_EINVAL, "bad draw_pixels arguments");
+    if (M < 1 || M > 0x7fffffff || n < 1 || n > M) return fail(NERF_AMD_EINVAL, "draw_pixels: need 1 <= n <= M <= 2^31 - 1");
+    if (!region && M != (int64_t)H * W) return fail(NERF_AMD_EINVAL, "draw_pixels: without a region list M must be H * W");
+    int rc = launch_draw_pixels(M, n, seed, draw_count, region, W, image, row_stride, C, pixels, target, static_cast<hipStream_t>(stream));
+    return rc ? fail(rc, "draw_pixels launch failed") : NERF_AMD_OK;
+}
+
+int64_t nerf_amd_interest_points_workspace(int32_t H, int32_t W) {
+    if (H < 1 || W < 1) return 0;
+    return 8 + (int64_t)H * W * (8 + 4 + 4);          // the maximum, the int64 responses, gx, gy
+}
+
+int nerf_amd_interest_points(const uint8_t *image, int32_t H, int32_t W, int32_t C, int32_t quality, void *workspace, uint8_t *mask,
+                             void *stream) {
+    if (H < 1 || W < 1 || (int64_t)H * W > 0x7fffffff || (C != 3 && C != 4) || quality < 1 || quality > 100 || !image || !workspace ||
+        !mask || (reinterpret_cast<uintptr_t>(workspace) & 7))
+        return fail(NERF_AMD_EINVAL, "bad interest_points arguments (C = 3 or 4, quality 1..100, workspace 8-byte aligned)");
+    int rc = launch_interest_points(image, H, W, C, quality, workspace, mask, static_cast<hipStream_t>(stream));
+    return rc ? fail(rc, "interest_points launch failed") : NERF_AMD_OK;
+}
+
+int nerf_amd_dilate_mask(const uint8_t *in, int32_t H, int32_t W, int32_t k, int32_t iterations, uint8_t *out, void *stream) {
+    if (H < 1 || W < 1 || (int64_t)H * W > 0x7fffffff || k < 1 || iterations < 1 || (int64_t)k * iterations > 0x7fff || !in || !out ||
+        in == out)
+        return fail(NERF_AMD_EINVAL, "bad dilate_mask arguments");
+    int rc = launch_dilate_mask(in, H, W, k, iterations, out, static_cast<hipStream_t>(stream));
+    return rc ? fail(rc, "dilate_mask launch failed") : NERF_AMD_OK;
+}
+
+int nerf_amd_compact_mask(const uint8_t *mask, int32_t H, int32_t W, int32_t *block_counts, int32_t *list, int64_t *count, void *stream) {
+    if (H < 1 || W < 1 || (int64_t)H * W > 0x7fffffff || !mask || !block_counts || !list || !count)
+        return fail(NERF_AMD_EINVAL, "bad compact_mask arguments");
+    int rc = launch_compact_mask(mask, H, W, block_counts, list, count, static_cast<hipStream_t>(stream));
+    return rc ? fail(rc, "compact_mask launch failed") : NERF_AMD_OK;
+}
+
 int nerf_amd_make_rays(int32_t H, int32_t W, const double *K4, const float *c2w, const float *c2w_static,
                        int64_t pix0, int64_t n, float near, float far, int use_viewdirs, int ndc,
                        float *rays_out, void *stream) {

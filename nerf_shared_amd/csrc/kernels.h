@@ -205,5 +205,11 @@ int launch_rays_at_pixels_bwd(const double *K4, const int32_t *pix, int64_t n, c
 int launch_se3_transform(const float *w, const float *v, const float *theta, const float *x, float *T, hipStream_t s);
 int launch_se3_transform_bwd(const float *w, const float *v, const float *theta, const float *x, const float *g_T, float *g_w,
                              float *g_v, float *g_theta, hipStream_t s);
+// pixel selection for pose estimation (pixel_select.hip; demo_est_rel_pose.py:35-47, :75-79)
+int launch_draw_pixels(int64_t M, int n, uint32_t seed, int64_t *draw_count, const int32_t *region, int W, const float *image,
+                       int64_t row_stride, int C, int32_t *pixels, float *target, hipStream_t s);
+int launch_interest_points(const uint8_t *image, int H, int W, int C, int quality, void *workspace, uint8_t *mask, hipStream_t s);
+int launch_dilate_mask(const uint8_t *in, int H, int W, int k, int iterations, uint8_t *out, hipStream_t s);
+int launch_compact_mask(const uint8_t *mask, int H, int W, int32_t *block_counts, int32_t *list, int64_t *count, hipStream_t s);
 
 }  // namespace na

@@ -271,6 +271,171 @@ class CameraTransf(torch.nn.Module):
         return _Se3Fn.apply(self.w, self.v, self.theta, x.detach().float().contiguous())
 
 
+# ---------------------------------------------------------------- which pixels a pose-estimation step looks at
+STRATEGIES = ("random", "interest_point", "interest_region")          # the demo's --sampling_strategy values
+
+
+def _sensor_image(image):
+    """Shape and dtype check of a sensor image, on the host: [H, W, 3|4], uint8 or floating point; numpy array or tensor."""
+    if not isinstance(image, torch.Tensor):
+        image = np.asarray(image)
+    if image.ndim != 3 or image.shape[2] not in (3, 4) or image.shape[0] < 1 or image.shape[1] < 1:
+        raise _lib.NerfAmdError("the sensor image must be [H, W, 3] or [H, W, 4], got %s" % (tuple(image.shape),))
+    floating = image.is_floating_point() if isinstance(image, torch.Tensor) else np.issubdtype(image.dtype, np.floating)
+    is_u8 = image.dtype in (torch.uint8, np.dtype(np.uint8))
+    if not (floating or is_u8):
+        raise _lib.NerfAmdError("the sensor image must be uint8 (0..255) or floating point (0..1), got %s" % (image.dtype,))
+    return image, is_u8
+
+
+def _image_u8_device(image, is_u8, device):
+    """uint8 [H, W, C] contiguous on `device`; a float image goes through to8b (utils.py:30)."""
+    if not is_u8:
+        image = to8b(image if (isinstance(image, torch.Tensor) and image.is_cuda) else
+                     (image.detach().cpu().numpy() if isinstance(image, torch.Tensor) else image))
+    return torch.as_tensor(image).to(device).contiguous()
+
+
+def _host_points(points, H, W):
+    """The caller's interest points [N, 2] (x, y) as a checked int64 host tensor (they address the mask)."""
+    if isinstance(points, torch.Tensor):
+        points = points.detach().cpu()
+    pts = _device_pixels(points, H, W, torch.device("cpu"))
+    if pts.shape[0] == 0:
+        raise _lib.NerfAmdError("no interest points were given")
+    return pts.long()
+
+
+def _interest_mask(img8, quality):
+    """nerf_amd_interest_points on a uint8 device image [H, W, C] -> uint8 mask [H, W]."""
+    H, W, C = img8.shape
+    dev = img8.device
+    ws = torch.empty(int(lib.nerf_amd_interest_points_workspace(H, W)) // 8, dtype=torch.int64, device=dev)
+    mask = torch.empty(H, W, dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev):
+        _lib.check(lib.nerf_amd_interest_points(img8.data_ptr(), H, W, C, int(quality), ws.data_ptr(), mask.data_ptr(),
+                                                _lib.stream_of(dev)), "nerf_amd_interest_points")
+    return mask
+
+
+def _dilate_mask(mask, k, iterations):
+    out = torch.empty_like(mask)
+    H, W = mask.shape
+    with torch.cuda.device(mask.device):
+        _lib.check(lib.nerf_amd_dilate_mask(mask.data_ptr(), H, W, int(k), int(iterations), out.data_ptr(),
+                                            _lib.stream_of(mask.device)), "nerf_amd_dilate_mask")
+    return out
+
+
+def _compact_mask(mask):
+    """coords[mask]: ([M, 2] int32 (x, y) in row-major order, M).  Synchronises once, to learn M."""
+    H, W = mask.shape
+    dev = mask.device
+    blocks = torch.empty((H * W + 255) // 256, dtype=torch.int32, device=dev)
+    full = torch.empty(H * W, 2, dtype=torch.int32, device=dev)
+    count = torch.empty((), dtype=torch.int64, device=dev)
+    with torch.cuda.device(dev):
+        _lib.check(lib.nerf_amd_compact_mask(mask.data_ptr(), H, W, blocks.data_ptr(), full.data_ptr(), count.data_ptr(),
+                                             _lib.stream_of(dev)), "nerf_amd_compact_mask")
+    M = int(count)
+    return full[:M].clone(), M
+
+
+def find_POI(image, quality=1):
+    """Interest points of a sensor image, [N, 2] int32 (x, y) in row-major order, a device tensor.
+
+    This is a STAND-IN for the demo's find_POI (demo_est_rel_pose.py:151-164), not a reproduction of it: the demo runs cv2's
+    SIFT detector, which this package neither needs nor can match.  The detector here is exact integer Harris corners
+    (include/nerf_amd.h, nerf_amd_interest_points): deterministic, already de-duplicated, `quality` = the percentage of
+    the strongest response a corner must reach.  With cv2 at hand, pass SIFT's points to PixelSampler(points=...) instead.
+    `image`: uint8 [H, W, 3|4] (numpy or tensor); a float image in 0..1 is quantised with to8b first."""
+    image, is_u8 = _sensor_image(image)
+    if not 1 <= int(quality) <= 100:
+        raise _lib.NerfAmdError("quality is an integer percentage, 1..100, got %r" % (quality,))
+    dev = image.device if (isinstance(image, torch.Tensor) and image.is_cuda) else _default_device()
+    return _compact_mask(_interest_mask(_image_u8_device(image, is_u8, dev), quality))[0]
+
+
+class PixelSampler:
+    """The pixel selection of the pose-estimation demo on the device: the sampling region once (demo_est_rel_pose.py:35-47),
+    then per step n_rays distinct pixels of it and their colours (:75-79) in one launch with nothing on the host.
+
+    strategy (the demo's --sampling_strategy):
+      random           every pixel of the image, M = H W (no list is stored);
+      interest_point   the de-duplicated interest points in row-major order;
+      interest_region  the point mask dilated `dil_iter` times with a kernel_size x kernel_size window (cv2.dilate's
+                       definition, exact), then coords[mask] in row-major order (exact).
+    points=None finds the points with utils.find_POI (a stand-in for the demo's SIFT); otherwise `points` [N, 2] (x, y) are the
+    caller's, checked on the host against the image.  H = image.shape[0], W = image.shape[1] (the demo swaps them, which only
+    square images hide).  uint8 images become the demo's (img / 255.).astype(float32), a float image is taken as it is; the
+    image is kept on the device as fp32 [H, W, 3] -- a fp32 device tensor whose pixels are C contiguous floats is used in place
+    (a view with a row stride or a fourth channel included), so it can be rewritten between draws.
+
+    draw() -> (pixels [n_rays, 2] int32 (x, y), target [n_rays, 3] fp32): the SAME two device tensors on every call, filled by
+    nerf_amd_draw_pixels -- no synchronisation, no allocation, capturable in torch.cuda.graph.  The draw is a keyed bijection
+    of [0, M) (defined in include/nerf_amd.h) of `seed` and the device counter `draw_count`, which every draw advances by one
+    on the device: draw k of a seed is always the same pixels, whether eager or replayed.  The key uses the low 32 bits of
+    the counter, so draws 2^32 apart repeat.  reset(count) sets the counter.  `region` is the [M, 2] list (None for random).
+    Construction synchronises once to learn M and raises NerfAmdError without interest points or with n_rays > M."""
+
+    def __init__(self, image, n_rays, strategy='interest_region', points=None, kernel_size=5, dil_iter=3, seed=0, device=None):
+        if strategy not in STRATEGIES:
+            raise _lib.NerfAmdError("unknown sampling strategy %r (one of %s)" % (strategy, ", ".join(STRATEGIES)))
+        image, is_u8 = _sensor_image(image)
+        H, W = int(image.shape[0]), int(image.shape[1])
+        if int(n_rays) < 1 or int(kernel_size) < 1 or int(dil_iter) < 1:
+            raise _lib.NerfAmdError("n_rays, kernel_size and dil_iter must be at least 1")
+        pts = _host_points(points, H, W) if (points is not None and strategy != "random") else None
+        if device is None:
+            device = image.device if (isinstance(image, torch.Tensor) and image.is_cuda) else _default_device()
+        dev = torch.device(device)
+        if dev.type != "cuda":
+            raise _lib.NerfAmdError("PixelSampler draws on a ROCm device, got %s -- there is no CPU path" % dev)
+        self.H, self.W, self.n_rays, self.strategy, self.seed = H, W, int(n_rays), strategy, int(seed) & 0xffffffff
+        self.region = None
+        self.M = H * W
+        if strategy != "random":
+            if pts is None:
+                mask = _interest_mask(_image_u8_device(image, is_u8, dev), 1)
+            else:
+                mask = torch.zeros(H, W, dtype=torch.uint8, device=dev)
+                pts = pts.to(dev)
+                mask[pts[:, 1], pts[:, 0]] = 1
+            if strategy == "interest_region":
+                mask = _dilate_mask(mask, kernel_size, dil_iter)
+            self.region, self.M = _compact_mask(mask)
+            if self.M == 0:
+                raise _lib.NerfAmdError("the image has no interest points (a featureless image?): use strategy='random' or pass points=")
+        if self.n_rays > self.M:
+            raise _lib.NerfAmdError("cannot draw %d distinct pixels out of %d (np.random.choice(replace=False) raises too)"
+                                    % (self.n_rays, self.M))
+        if is_u8:                                  # the 256 values of (img / 255.).astype(float32), computed as the demo does
+            lut = torch.from_numpy((np.arange(256) / 255.).astype(np.float32)).to(dev)
+            self.image = lut[torch.as_tensor(image).to(dev)[..., :3].long()].contiguous()
+        else:
+            img = torch.as_tensor(image).to(dev)
+            C = img.shape[2]
+            in_place = (img.dtype == torch.float32 and img.stride(2) == 1 and img.stride(1) == C and img.stride(0) >= W * C
+                        and img.data_ptr() % 4 == 0)
+            self.image = img.detach() if in_place else img.detach()[..., :3].float().contiguous()
+        self.draw_count = torch.zeros((), dtype=torch.int64, device=dev)
+        self.pixels = torch.zeros(self.n_rays, 2, dtype=torch.int32, device=dev)
+        self.target = torch.zeros(self.n_rays, 3, dtype=torch.float32, device=dev)
+
+    def draw(self):
+        dev = self.pixels.device
+        img = self.image
+        with torch.cuda.device(dev):
+            _lib.check(lib.nerf_amd_draw_pixels(self.M, self.n_rays, self.seed, self.draw_count.data_ptr(), _lib.ptr(self.region),
+                                                self.H, self.W, img.data_ptr(), img.stride(0), img.shape[2], self.pixels.data_ptr(),
+                                                self.target.data_ptr(), _lib.stream_of(dev)), "nerf_amd_draw_pixels")
+        return self.pixels, self.target
+
+    def reset(self, count=0):
+        """The next draw is draw `count` (a device write, stream-ordered; no synchronisation)."""
+        self.draw_count.fill_(int(count))
+
+
 def get_rays_np(H, W, K, c2w):
     """numpy twin used by the reference's training-data batching (utils.py:45-52)."""
     i, j = np.meshgrid(np.arange(W, dtype=np.float32), np.arange(H, dtype=np.float32), indexing='xy')
@@ -522,9 +687,15 @@ class CapturedPoseStep:
         for k in range(n_iters):
             loss = step(pixels_k, target_k)                      # device scalar
             for g in opt.param_groups: g['lr'] = lrate * 0.8 ** ((k + 1) / 100)
+
+    With sampler=utils.PixelSampler(image, n_rays, ...) the captured body BEGINS with sampler.draw(): every replay draws its own
+    n_rays pixels and gathers their colours on the device, step.pixels / step.target are the sampler's buffers (the batch of
+    the last replay), and step() takes no arguments -- the loop touches the host for the learning-rate write alone.  The
+    warm-up draws of the construction do not count: sampler.draw_count is afterwards what it was before.
     """
 
-    def __init__(self, renderer, H, W, K, chunk, coarse_model, fine_model, cam_transf, start_pose, optimizer, n_rays, warmup=3):
+    def __init__(self, renderer, H, W, K, chunk, coarse_model, fine_model, cam_transf, start_pose, optimizer, n_rays, warmup=3,
+                 sampler=None):
         from . import optim
         if not isinstance(optimizer, optim.Adam):
             raise _lib.NerfAmdError("CapturedPoseStep needs nerf_shared_amd.optim.Adam over cam_transf.parameters(): torch's "
@@ -544,12 +715,24 @@ class CapturedPoseStep:
         self.start_pose = torch.as_tensor(start_pose, dtype=torch.float32).to(dev).contiguous().clone()
         if tuple(self.start_pose.shape) != (4, 4):
             raise _lib.NerfAmdError("start_pose must be [4, 4], got %s" % (tuple(self.start_pose.shape),))
-        # a valid placeholder batch for the warm-up: pixel (0, 0) n_rays times, a grey target
-        self.pixels = torch.zeros(n_rays, 2, device=dev, dtype=torch.int32)
-        self.target = torch.full((n_rays, 3), 0.5, device=dev)
+        self.sampler = sampler
+        if sampler is not None:
+            if not isinstance(sampler, PixelSampler) or sampler.pixels.device != dev:
+                raise _lib.NerfAmdError("sampler must be a utils.PixelSampler on the parameters' device (%s)" % dev)
+            if sampler.n_rays != int(n_rays) or (sampler.H, sampler.W) != (int(H), int(W)):
+                raise _lib.NerfAmdError("the sampler draws %d pixels of a %d x %d image; this step was asked for %d rays of %d x %d"
+                                        % (sampler.n_rays, sampler.H, sampler.W, int(n_rays), int(H), int(W)))
+            self.pixels, self.target = sampler.pixels, sampler.target
+            draws_before = sampler.draw_count.clone()
+        else:
+            # a valid placeholder batch for the warm-up: pixel (0, 0) n_rays times, a grey target
+            self.pixels = torch.zeros(n_rays, 2, device=dev, dtype=torch.int32)
+            self.target = torch.full((n_rays, 3), 0.5, device=dev)
         self.loss = self.pose = None
         self._lr = None
         self.graph = _capture_step(self._body, optimizer, self.params, (), dev, warmup)
+        if sampler is not None:
+            sampler.draw_count.copy_(draws_before)                # the warm-up draws do not count
         with torch.no_grad():
             self.pose.copy_(cam_transf(self.start_pose))          # (the capture left the pose of its own last update there)
 
@@ -558,6 +741,8 @@ class CapturedPoseStep:
         coarse, fine = self.models
         for p in self.params:
             p.grad = None
+        if self.sampler is not None:
+            self.sampler.draw()                   # fills self.pixels / self.target (the sampler's buffers)
         pose = self.cam_transf(self.start_pose)
         rays_o, rays_d = get_rays_at(H, W, K, pose, self.pixels)
         rgb, disp, acc, extras = self.renderer.render_from_rays(H, W, K, chunk, torch.stack([rays_o, rays_d], 0), coarse, fine,
@@ -569,11 +754,17 @@ class CapturedPoseStep:
         with torch.no_grad():
             self.pose = self.cam_transf(self.start_pose)
 
-    def __call__(self, pixels, target):
+    def __call__(self, pixels=None, target=None):
         H, W = self.args[0], self.args[1]
-        pix = pixels if (isinstance(pixels, torch.Tensor) and pixels.is_cuda) else _device_pixels(pixels, H, W, self.pixels.device)
-        self.pixels.copy_(pix, non_blocking=True)
-        self.target.copy_(target, non_blocking=True)
+        if self.sampler is not None:
+            if pixels is not None or target is not None:
+                raise _lib.NerfAmdError("this step draws its own pixels (sampler=...): call step() without arguments")
+        else:
+            if pixels is None or target is None:
+                raise _lib.NerfAmdError("step(pixels, target): a step built without a sampler needs both")
+            pix = pixels if (isinstance(pixels, torch.Tensor) and pixels.is_cuda) else _device_pixels(pixels, H, W, self.pixels.device)
+            self.pixels.copy_(pix, non_blocking=True)
+            self.target.copy_(target, non_blocking=True)
         lr = tuple(float(g["lr"]) for g in self.optimizer.param_groups)
         if lr != self._lr:
             self.optimizer.sync_lr()
@@ -581,6 +772,47 @@ class CapturedPoseStep:
         self.graph.replay()
         self.optimizer.note_replayed_step()
         return self.loss
+
+
+class PoseEstimate(tuple):
+    """(pose, losses) of utils.estimate_relative_pose; `.step` is the CapturedPoseStep it ran (with .sampler, .cam_transf,
+    .optimizer), for callers that want to go on or look inside."""
+
+    def __new__(cls, pose, losses, step):
+        self = super().__new__(cls, (pose, losses))
+        self.step = step
+        return self
+
+    pose = property(lambda self: self[0])
+    losses = property(lambda self: self[1])
+
+
+def estimate_relative_pose(coarse_model, fine_model, renderer, sensor_image, start_pose, K, chunk, *, steps=300, batch_size=512,
+                           lrate=0.01, strategy='interest_region', kernel_size=5, dil_iter=3, points=None, seed=0):
+    """The pose-estimation demo's function (demo_est_rel_pose.py:26-98), sensor image in, pose out: the sampling region
+    (PixelSampler), the se(3) module (CameraTransf), Adam over its seven numbers, and `steps` replays of one captured step
+    with the demo's schedule, lr = lrate * 0.8 ** ((k + 1) / 100) set after step k.  A replay draws, renders, differentiates
+    and updates on the device; the host writes the learning rate and nothing else, and nothing is read back inside the loop.
+
+    Returns (pose, losses): the final [4, 4] camera-to-world (device) and the per-step losses [steps] (device).  The models must
+    be frozen (requires_grad_(False)), as CapturedPoseStep demands; `points` are the caller's interest points (cv2 SIFT's, as
+    in the demo) instead of the built-in detector's; `seed` fixes the draws.  (The returned tuple also carries `.step`, the
+    captured step, for going on from there.)"""
+    from . import optim
+    H, W = int(sensor_image.shape[0]), int(sensor_image.shape[1])
+    dev = next(coarse_model.parameters()).device
+    sampler = PixelSampler(sensor_image, batch_size, strategy=strategy, points=points, kernel_size=kernel_size, dil_iter=dil_iter,
+                           seed=seed, device=dev)
+    cam_transf = CameraTransf().to(dev)
+    optimizer = optim.Adam(cam_transf.parameters(), lr=lrate, betas=(0.9, 0.999))
+    step = CapturedPoseStep(renderer, H, W, K, chunk, coarse_model, fine_model, cam_transf, start_pose, optimizer, batch_size,
+                            sampler=sampler)
+    losses = torch.zeros(int(steps), device=dev, dtype=torch.float32)
+    for k in range(int(steps)):
+        losses[k].copy_(step())
+        for g in optimizer.param_groups:
+            g['lr'] = lrate * (0.8 ** ((k + 1) / 100))
+    return PoseEstimate(step.pose.clone(), losses, step)
 
 
 def save_checkpoints(args, coarse_model, fine_model, optimizer, global_step, i):

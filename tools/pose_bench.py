@@ -7,12 +7,17 @@ synthetic weights.  Three legs per (batch, precision):
      image (pose through the host), index the selected pixels, render, img2mse, backward with the weight-gradient launches
      (for this leg the tool sends the inputs-only backward through nerf_amd_field_backward), torch.optim.Adam;
   b  the device-side ops eagerly: utils.CameraTransf, utils.get_rays_at, inputs-only field backward, optim.Adam;
-  c  utils.CapturedPoseStep: leg b's body captured in a HIP graph, one replay per step.
+  c  utils.CapturedPoseStep: leg b's body captured in a HIP graph, one replay per step;
+  c' leg c fed the demo's way (demo_est_rel_pose.py:75-79), what a caller had to write before the sampler: np.random.choice over
+     the interest region without replacement, numpy indexing of the region and of the image, torch.Tensor(...).to(device);
+  d  utils.CapturedPoseStep(sampler=utils.PixelSampler(...)): the draw and the gather are the first launch of the captured body.
+Legs c' and d share one interest region of the 400 x 400 image (500 seeded points, dilated 3 times with a 5 x 5 window: 40 000 to
+80 000 pixels), the batch and the models; they also record wall ms per step (enqueue the whole loop, then wait for the device).
 
 The synthetic fields get a density bias of +1: at scale 1.0 every sigma is negative and the volume would be empty (a white
 image, no pose gradient); with it the three legs' losses follow the same optimisation and can be compared.
 
-Per leg: host ms per step (wall time of enqueueing the steps, no synchronisation added) and GPU ms per step (events around
+Legs a, b and c are fed from eight prepared pixel sets (no selection cost).  Per leg: host ms per step (wall time of enqueueing the steps, no synchronisation added) and GPU ms per step (events around
 the timed steps).  Prints one JSON line.
 
     python tools/pose_bench.py [--steps 60] [--warmup 5] [--out profiles/pose_step.json]
@@ -82,7 +87,7 @@ def full_backward_for_frozen_models(models):
         _lib.lib.nerf_amd_field_backward_inputs = inputs_only
 
 
-def timed(step, steps, warmup):
+def timed(step, steps, warmup, wall=False):
     for k in range(warmup):
         step(k)
     torch.cuda.synchronize()
@@ -94,7 +99,44 @@ def timed(step, steps, warmup):
     host = (time.perf_counter() - t0) / steps
     e1.record()
     torch.cuda.synchronize()
-    return {"host_ms_per_step": host * 1e3, "gpu_ms_per_step": e0.elapsed_time(e1) / steps, "loss": float(loss.detach())}
+    total = (time.perf_counter() - t0) / steps
+    out = {"host_ms_per_step": host * 1e3, "gpu_ms_per_step": e0.elapsed_time(e1) / steps, "loss": float(loss.detach())}
+    if wall:
+        out["wall_ms_per_step"] = total * 1e3
+    return out
+
+
+def interest_points(n=500, seed=0):
+    """Seeded stand-ins for a detector's points, [n, 2] (x, y): the region they give is the same in every run."""
+    rng = np.random.default_rng(seed)
+    idx = rng.choice(H * W, size=n, replace=False)
+    return np.stack([idx % W, idx // W], -1)
+
+
+def draw_kernel_us(sampler, draws=100, repeats=3):
+    """GPU time of one sampler.draw() (the draw / gather launch and the counter's one-thread launch), from events around a
+    graph of `draws` of them; the counter is put back."""
+    before = sampler.draw_count.clone()
+    side = torch.cuda.Stream(sampler.pixels.device)
+    side.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(side):
+        sampler.draw()
+    torch.cuda.current_stream().wait_stream(side)
+    graph = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(graph):
+        for _ in range(draws):
+            sampler.draw()
+    best = None
+    for _ in range(repeats):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        graph.replay()
+        e1.record()
+        torch.cuda.synchronize()
+        t = e0.elapsed_time(e1) / draws * 1e3
+        best = t if best is None else min(best, t)
+    sampler.draw_count.copy_(before)
+    return best
 
 
 def run(dev, batch, precision, steps, warmup):
@@ -171,6 +213,40 @@ def run(dev, batch, precision, steps, warmup):
         decay(opt_c, k)
         return loss
     out["c_captured_pose_step"] = timed(step_c, steps, warmup)
+
+    # c': the captured step fed the demo's way (host selection, two host-to-device copies per step)
+    obs_img = (np.random.default_rng(1).integers(0, 256, size=(H, W, 3)).astype(np.uint8) / 255.).astype(np.float32)
+    points = interest_points()
+    sampler = utils.PixelSampler(obs_img, batch, strategy="interest_region", points=points, kernel_size=5, dil_iter=3, seed=0, device=dev)
+    interest_regions = sampler.region.cpu().numpy()
+    torch.manual_seed(0)
+    cam_h = utils.CameraTransf().to(dev)
+    opt_h = optim.Adam(cam_h.parameters(), lr=LRATE, betas=(0.9, 0.999))
+    captured_h = utils.CapturedPoseStep(r, H, W, K, 32768, models[0], models[1], cam_h, start, opt_h, batch)
+    np.random.seed(0)
+
+    def step_h(k):
+        rand_inds = np.random.choice(interest_regions.shape[0], size=batch, replace=False)
+        sel = interest_regions[rand_inds]
+        target_s = torch.Tensor(obs_img[sel[:, 1], sel[:, 0]]).to(dev)
+        loss = captured_h(sel, target_s)
+        decay(opt_h, k)
+        return loss
+    out["c_prime_captured_host_selection"] = timed(step_h, steps, warmup, wall=True)
+
+    # d: the captured step that draws its own pixels
+    torch.manual_seed(0)
+    cam_d = utils.CameraTransf().to(dev)
+    opt_d = optim.Adam(cam_d.parameters(), lr=LRATE, betas=(0.9, 0.999))
+    captured_d = utils.CapturedPoseStep(r, H, W, K, 32768, models[0], models[1], cam_d, start, opt_d, batch, sampler=sampler)
+
+    def step_d(k):
+        loss = captured_d()
+        decay(opt_d, k)
+        return loss
+    out["d_captured_with_sampler"] = timed(step_d, steps, warmup, wall=True)
+    out["region_pixels"] = sampler.M
+    out["draw_us_per_call"] = draw_kernel_us(sampler)
     return out
 
 
