@@ -1119,9 +1119,7 @@ int64_t carve(const Program &p, int64_t P_points, char *base, TrainWs *w, bool s
 
 bool train_supported(const Program &p) {
     const nerf_amd_arch &a = p.arch;
-    if (!p.bf16_ok || a.i_embed != 0) return false;
-    if (a.use_viewdirs) return (a.multires == 10 && a.multires_views == 4) || (a.multires == 15 && a.multires_views == 6);
-    return (a.multires == 10 || a.multires == 15) && p.out_ch <= 16;       // output_linear models (nerf.py:91-94)
+    return fused_program(p) && family_known(a.multires, a.multires_views, a.use_viewdirs) && head_fits(a.use_viewdirs, p.out_ch);
 }
 
 int64_t train_workspace_bytes(const Program &p, int64_t P, bool split) { return carve(p, P, nullptr, nullptr, split); }

@@ -13,6 +13,7 @@
 #include <vector>
 
 #include "kernels.h"
+#include "launch_util.h"
 #include "program.h"
 
 using namespace na;
@@ -54,7 +55,41 @@ int upload(T **dst, const std::vector<T> &src) {
     return NERF_AMD_OK;
 }
 size_t align_up(size_t v) { return (v + 255) & ~(size_t)255; }
+
+// ---- {ticket, done} pairs of the dynamic deal (launch_util.h)
+constexpr int TILE_CTR_SLOTS = 1024;
+unsigned *g_tile_ctr[16] = {};
+std::atomic<unsigned> g_tile_ctr_next{0};
 }  // namespace
+
+namespace na {
+// tuning knob (nerf_amd_set_tuning key 0): 0 = 16x16x32 kernel, 100+ = the shapes of mlp_bf16.hip (launch_one).  Atomic: the
+// launchers of concurrent host threads read it while nerf_amd_set_tuning may write it (nerf_amd.h threading contract).
+std::atomic<int> g_variant{0};
+
+int tile_counters_init(int device) {
+    if (device < 0 || device >= 16) return NERF_AMD_EINVAL;
+    if (g_tile_ctr[device]) return NERF_AMD_OK;
+    unsigned *p = nullptr;
+    if (hipMalloc(reinterpret_cast<void **>(&p), TILE_CTR_SLOTS * 2 * sizeof(unsigned)) != hipSuccess) return NERF_AMD_EHIP;
+    if (hipMemset(p, 0, TILE_CTR_SLOTS * 2 * sizeof(unsigned)) != hipSuccess) { (void)hipFree(p); return NERF_AMD_EHIP; }
+    g_tile_ctr[device] = p;
+    return NERF_AMD_OK;
+}
+
+unsigned *tile_counter_slot(int device) {
+    if (device < 0 || device >= 16 || !g_tile_ctr[device]) return nullptr;
+    return g_tile_ctr[device] + 2 * (g_tile_ctr_next.fetch_add(1, std::memory_order_relaxed) % TILE_CTR_SLOTS);
+}
+
+unsigned *tile_counter_for(bool deal, hipStream_t s) {
+    if (!deal) return nullptr;
+    hipStreamCaptureStatus st = hipStreamCaptureStatusNone;
+    if (hipStreamIsCapturing(s, &st) != hipSuccess || st != hipStreamCaptureStatusNone) return nullptr;
+    int dev = 0;
+    return hipGetDevice(&dev) == hipSuccess ? tile_counter_slot(dev) : nullptr;
+}
+}  // namespace na
 
 struct nerf_amd_model {
     Program prog;
@@ -173,12 +208,12 @@ void nerf_amd_model_destroy(nerf_amd_model *m) {
 int nerf_amd_model_supports_bf16(const nerf_amd_model *m) {
     if (!m) return 0;
     const nerf_amd_arch &a = m->prog.arch;
-    return m->prog.bf16_ok && a.i_embed == 0 && mlp_bf16_supported(a.multires, a.multires_views, a.use_viewdirs);
+    return fused_program(m->prog) && mlp_bf16_supported(a.multires, a.multires_views, a.use_viewdirs);
 }
 int nerf_amd_model_supports_split(const nerf_amd_model *m) {
     if (!m) return 0;
     const nerf_amd_arch &a = m->prog.arch;
-    return m->prog.bf16_ok && a.i_embed == 0 && mlp_split_supported(a.multires, a.multires_views, a.use_viewdirs, m->prog.out_ch);
+    return fused_program(m->prog) && mlp_split_supported(a.multires, a.multires_views, a.use_viewdirs, m->prog.out_ch);
 }
 int nerf_amd_model_out_ch(const nerf_amd_model *m) { return m ? m->prog.out_ch : 0; }
 
@@ -217,18 +252,35 @@ int need_copy(const nerf_amd_model *m, int copy) {
                                           : "model has no parameters yet (call nerf_amd_model_update)");
 }
 
-int run_field(const nerf_amd_model *m, MlpArgs a, int precision, hipStream_t s) {
+// the packed copy a forward pass in `precision` reads
+int copy_for(int precision) {
+    return precision == NERF_AMD_PREC_BF16 ? NERF_AMD_COPY_BF16 : precision == NERF_AMD_PREC_FP32_SPLIT ? NERF_AMD_COPY_SPLIT : NERF_AMD_COPY_FP32;
+}
+
+// The points of a launch: explicit pts [P,3] (+ viewdirs [R,3]), or rays [R,ray_ch] + z_vals [R,S] (view directions at
+// column 8 of a ray).  vd: the model has a view branch.
+void set_inputs(MlpArgs &a, const float *pts, const float *viewdirs, const float *rays, int ray_ch, const float *z_vals, bool vd) {
+    if (pts) { a.pts = pts; a.viewdirs = vd ? viewdirs : nullptr; a.vd_stride = 3; }
+    else { a.rays = rays; a.ray_stride = ray_ch; a.z_vals = z_vals; a.viewdirs = vd ? rays + 8 : nullptr; a.vd_stride = ray_ch; }
+}
+
+// what the kernels that walk the fp32 program need to know of the model
+void set_model_constants(MlpArgs &a, const nerf_amd_model *m) {
     const Program &p = m->prog;
-    if (int rc0 = need_copy(m, precision == NERF_AMD_PREC_BF16 ? NERF_AMD_COPY_BF16 : precision == NERF_AMD_PREC_FP32_SPLIT ? NERF_AMD_COPY_SPLIT : NERF_AMD_COPY_FP32))
-        return rc0;
-    a.stream_bf16 = m->stream_bf16; a.bias_bf16 = m->bias_bf16;
-    a.stream_s16 = m->stream_s16; a.bias_s16 = m->bias_s16;
-    a.stream_split = m->stream_split;
-    a.stream_f32 = m->stream_f32; a.bias_f32 = m->bias_f32;
     a.layers = m->d_layers; a.n_layers = (int)p.layers.size();
     a.input_ch = p.input_ch; a.input_ch_views = p.input_ch_views; a.W = p.arch.W; a.lds_rows = p.lds_rows;
     a.multires = p.arch.multires; a.multires_views = p.arch.multires_views; a.i_embed = p.arch.i_embed;
     a.out_ch = p.out_ch;
+}
+
+int run_field(const nerf_amd_model *m, MlpArgs a, int precision, hipStream_t s) {
+    const Program &p = m->prog;
+    if (int rc0 = need_copy(m, copy_for(precision))) return rc0;
+    a.stream_bf16 = m->stream_bf16; a.bias_bf16 = m->bias_bf16;
+    a.stream_s16 = m->stream_s16; a.bias_s16 = m->bias_s16;
+    a.stream_split = m->stream_split;
+    a.stream_f32 = m->stream_f32; a.bias_f32 = m->bias_f32;
+    set_model_constants(a, m);
     if (p.arch.use_viewdirs && !a.viewdirs) return fail(NERF_AMD_EINVAL, "model has a view branch but no viewdirs were given");
     if (!p.arch.use_viewdirs) a.viewdirs = nullptr;
     int rc;
@@ -287,9 +339,8 @@ int nerf_amd_nerf_forward(const nerf_amd_model *m, const float *pts, const float
     if (!m || n_rays < 0 || n_samples < 1) return fail(NERF_AMD_EINVAL, "bad forward arguments");
     if (n_rays == 0) return NERF_AMD_OK;
     if (!pts || !out) return fail(NERF_AMD_EINVAL, "null pts/out");
-    MlpArgs a;
-    std::memset(&a, 0, sizeof(a));
-    a.pts = pts; a.viewdirs = viewdirs; a.vd_stride = 3;
+    MlpArgs a{};
+    set_inputs(a, pts, viewdirs, nullptr, 0, nullptr, true);      // (run_field drops viewdirs for a model without view branch)
     a.P = n_rays * n_samples; a.S = n_samples; a.out = out;
     return run_field(m, a, precision, static_cast<hipStream_t>(stream));
 }
@@ -298,8 +349,7 @@ int nerf_amd_mlp_embedded(const nerf_amd_model *m, const float *x, int64_t n, fl
     if (!m || n < 0) return fail(NERF_AMD_EINVAL, "bad MLP arguments");
     if (n == 0) return NERF_AMD_OK;
     if (!x || !out) return fail(NERF_AMD_EINVAL, "null x/out");
-    MlpArgs a;
-    std::memset(&a, 0, sizeof(a));
+    MlpArgs a{};
     a.embedded = x;
     a.viewdirs = x;            // non-null marker: the view columns are inside x
     a.vd_stride = 0;
@@ -372,30 +422,24 @@ int nerf_amd_field_forward_train(const nerf_amd_model *m, const float *pts, cons
         const int64_t P = R * S;
         if ((!pts && (!rays || !z_vals)) || !raw || !workspace || workspace_bytes < train_f32_workspace_bytes(m->prog, P))
             return fail(NERF_AMD_EINVAL, "null pointer or workspace too small");
-        const Program &p = m->prog;
-        MlpArgs a;
-        std::memset(&a, 0, sizeof(a));
-        a.stream_f32 = m->stream_f32; a.bias_f32 = m->bias_f32; a.layers = m->d_layers; a.n_layers = (int)p.layers.size();
-        a.input_ch = p.input_ch; a.input_ch_views = p.input_ch_views; a.W = p.arch.W; a.lds_rows = p.lds_rows;
-        a.multires = p.arch.multires; a.multires_views = p.arch.multires_views; a.i_embed = p.arch.i_embed;
-        if (pts) { a.pts = pts; a.viewdirs = vd ? viewdirs : nullptr; a.vd_stride = 3; }
-        else { a.rays = rays; a.ray_stride = ray_ch; a.z_vals = z_vals; a.viewdirs = vd ? rays + 8 : nullptr; a.vd_stride = ray_ch; }
-        a.P = P; a.S = S; a.out = raw; a.out_ch = p.out_ch;
-        int rc = launch_train_f32_forward(p, a, m->d_tlayers, workspace, static_cast<hipStream_t>(stream));
+        MlpArgs a{};
+        a.stream_f32 = m->stream_f32; a.bias_f32 = m->bias_f32;
+        set_model_constants(a, m);
+        set_inputs(a, pts, viewdirs, rays, ray_ch, z_vals, vd);
+        a.P = P; a.S = S; a.out = raw;
+        int rc = launch_train_f32_forward(m->prog, a, m->d_tlayers, workspace, static_cast<hipStream_t>(stream));
         return rc ? fail(rc, "exact-fp32 training forward launch failed") : NERF_AMD_OK;
     }
-    if (int rc0 = need_copy(m, precision == NERF_AMD_PREC_FP32_SPLIT ? NERF_AMD_COPY_SPLIT : NERF_AMD_COPY_BF16)) return rc0;
+    if (int rc0 = need_copy(m, copy_for(precision))) return rc0;
     if (R == 0) return NERF_AMD_OK;
     const bool split = precision == NERF_AMD_PREC_FP32_SPLIT;
     const int64_t P = R * S;
     if (int rc0 = split ? split_point_limit(P) : NERF_AMD_OK) return rc0;
     if ((!pts && (!rays || !z_vals)) || !raw || !workspace || workspace_bytes < train_workspace_bytes(m->prog, P, split))
         return fail(NERF_AMD_EINVAL, "null pointer or workspace too small");
-    MlpArgs a;
-    std::memset(&a, 0, sizeof(a));
+    MlpArgs a{};
     a.stream_s16 = m->stream_s16; a.bias_s16 = m->bias_s16; a.stream_split = m->stream_split;
-    if (pts) { a.pts = pts; a.viewdirs = vd ? viewdirs : nullptr; a.vd_stride = 3; }
-    else { a.rays = rays; a.ray_stride = ray_ch; a.z_vals = z_vals; a.viewdirs = vd ? rays + 8 : nullptr; a.vd_stride = ray_ch; }
+    set_inputs(a, pts, viewdirs, rays, ray_ch, z_vals, vd);
     a.P = P; a.S = S; a.out = raw; a.out_ch = m->prog.out_ch;
     train_fill_args(m->prog, P, workspace, &a, split);
     const nerf_amd_arch &ar = m->prog.arch;
@@ -426,18 +470,13 @@ static int field_backward(const nerf_amd_model *m, const float *g_raw, const flo
             return fail(NERF_AMD_EINVAL, "null pointer or workspace too small");
         for (int i = 0; with_params && i < n_tensors; ++i)
             if (!grad_weights[i] || !grad_biases[i]) return fail(NERF_AMD_EINVAL, "null gradient pointer");
-        const Program &p = m->prog;
-        MlpArgs a;
-        std::memset(&a, 0, sizeof(a));
-        a.layers = m->d_layers; a.n_layers = (int)p.layers.size(); a.lds_rows = p.lds_rows; a.out_ch = p.out_ch;
-        a.input_ch = p.input_ch; a.input_ch_views = p.input_ch_views; a.W = p.arch.W;
-        a.multires = p.arch.multires; a.multires_views = p.arch.multires_views; a.i_embed = p.arch.i_embed;
-        if (pts) { a.pts = pts; a.viewdirs = vd ? viewdirs : nullptr; a.vd_stride = 3; }
-        else { a.rays = rays; a.ray_stride = ray_ch; a.z_vals = z_vals; a.viewdirs = vd ? rays + 8 : nullptr; a.vd_stride = ray_ch; }
+        MlpArgs a{};
+        set_model_constants(a, m);
+        set_inputs(a, pts, viewdirs, rays, ray_ch, z_vals, vd);
         a.g_pts = g_pts; a.g_rays = g_rays; a.g_vd = vd ? g_viewdirs : nullptr;
         a.P = n_points; a.S = S; a.g_raw = g_raw;
         // (the dW / db products of this path are launches of their own after the dX chain: without tables they are skipped)
-        int rc = launch_train_f32_backward(p, a, m->d_tlayers, m->stream_f32_t, workspace, with_params ? grad_weights : nullptr,
+        int rc = launch_train_f32_backward(m->prog, a, m->d_tlayers, m->stream_f32_t, workspace, with_params ? grad_weights : nullptr,
                                            with_params ? grad_biases : nullptr, static_cast<hipStream_t>(stream));
         return rc ? fail(rc, "exact-fp32 backward launch failed") : NERF_AMD_OK;
     }
@@ -447,11 +486,9 @@ static int field_backward(const nerf_amd_model *m, const float *g_raw, const flo
     if (!g_raw || !workspace || workspace_bytes < train_workspace_bytes(m->prog, n_points, split))
         return fail(NERF_AMD_EINVAL, "null pointer or workspace too small");
     hipStream_t s = static_cast<hipStream_t>(stream);
-    MlpArgs a;
-    std::memset(&a, 0, sizeof(a));
+    MlpArgs a{};
     a.stream_bwd = m->stream_bwd; a.stream_bwd_split = m->stream_bwd_split; a.g_raw = g_raw; a.P = n_points; a.S = S; a.out_ch = m->prog.out_ch;
-    if (pts) { a.pts = pts; a.viewdirs = vd ? viewdirs : nullptr; a.vd_stride = 3; }
-    else { a.rays = rays; a.ray_stride = ray_ch; a.z_vals = z_vals; a.viewdirs = vd ? rays + 8 : nullptr; a.vd_stride = ray_ch; }
+    set_inputs(a, pts, viewdirs, rays, ray_ch, z_vals, vd);
     a.g_pts = g_pts; a.g_rays = g_rays; a.g_vd = vd ? g_viewdirs : nullptr;
     train_fill_args(m->prog, n_points, workspace, &a, split);
     const nerf_amd_arch &ar = m->prog.arch;
@@ -498,7 +535,7 @@ const char *NO_VIEW_BRANCH = "density entry points take a model WITHOUT view bra
 
 bool density_fused_covers(const nerf_amd_model *m, int precision) {
     const nerf_amd_arch &a = m->prog.arch;
-    return precision == NERF_AMD_PREC_BF16 && m->prog.bf16_ok && a.i_embed == 0 && !m->prog.frags_bwd.empty() &&
+    return precision == NERF_AMD_PREC_BF16 && fused_program(m->prog) && !m->prog.frags_bwd.empty() &&
            density_grad_fused_supported(a.multires, a.use_viewdirs, m->prog.out_ch);
 }
 bool density_takes_fused(const nerf_amd_model *m, int precision) {
@@ -524,15 +561,14 @@ int nerf_amd_density(const nerf_amd_model *m, const float *pts, int64_t n, float
     if (m->prog.arch.use_viewdirs) return fail(NERF_AMD_EINVAL, NO_VIEW_BRANCH);
     if (precision != NERF_AMD_PREC_BF16 && precision != NERF_AMD_PREC_FP32_SPLIT && precision != NERF_AMD_PREC_FP32)
         return fail(NERF_AMD_EINVAL, "unknown precision");
-    if (int rc0 = need_copy(m, precision == NERF_AMD_PREC_BF16 ? NERF_AMD_COPY_BF16 : precision == NERF_AMD_PREC_FP32_SPLIT ? NERF_AMD_COPY_SPLIT : NERF_AMD_COPY_FP32))
-        return rc0;
+    if (int rc0 = need_copy(m, copy_for(precision))) return rc0;
     if (n == 0) return NERF_AMD_OK;
     if (!pts || !sigma) return fail(NERF_AMD_EINVAL, "null pts/sigma");
     hipStream_t s = static_cast<hipStream_t>(stream);
     const int och = m->prog.out_ch;
-    MlpArgs a;
-    std::memset(&a, 0, sizeof(a));
-    a.pts = pts; a.vd_stride = 3; a.P = n; a.S = 1;
+    MlpArgs a{};
+    set_inputs(a, pts, nullptr, nullptr, 0, nullptr, false);
+    a.P = n; a.S = 1;
     if (och == 1) {                 // the field kernel's own store is sigma [n]
         a.out = sigma;
         return run_field(m, a, precision, s);
@@ -569,8 +605,7 @@ int nerf_amd_density_value_grad(const nerf_amd_model *m, const float *pts, int64
         if (int rc0 = need_copy(m, NERF_AMD_COPY_BWD)) return rc0;
         if (n == 0) return NERF_AMD_OK;
         if (!pts || !sigma || !grad) return fail(NERF_AMD_EINVAL, "null pts/sigma/grad");
-        MlpArgs a;
-        std::memset(&a, 0, sizeof(a));
+        MlpArgs a{};
         a.stream_s16 = m->stream_s16; a.bias_s16 = m->bias_s16; a.stream_bwd = m->stream_bwd;
         a.pts = pts; a.P = n; a.S = 1; a.out = sigma; a.out_ch = och; a.g_pts = grad;
         int rc = launch_density_grad(a, m->prog.arch.multires, m->prog.n_frags16_used, (int)m->prog.tiles16.size(), m->prog.n_frags_bwd_used, s);
@@ -579,7 +614,7 @@ int nerf_amd_density_value_grad(const nerf_amd_model *m, const float *pts, int64
     // two launches: the training forward (saves the activations), then the dX chain alone with dL/draw = 1 in the sigma column
     const int path = train_path(m, precision);
     if (!path) return fail(NERF_AMD_EUNSUPPORTED, TRAIN_COVER);
-    const int fwd_copy = path == 2 ? NERF_AMD_COPY_FP32 : precision == NERF_AMD_PREC_FP32_SPLIT ? NERF_AMD_COPY_SPLIT : NERF_AMD_COPY_BF16;
+    const int fwd_copy = copy_for(precision);
     const int bwd_copy = path == 2 ? NERF_AMD_COPY_FP32_BWD : precision == NERF_AMD_PREC_FP32_SPLIT ? NERF_AMD_COPY_BWD_SPLIT : NERF_AMD_COPY_BWD;
     if (int rc0 = need_copy(m, fwd_copy)) return rc0;
     if (int rc0 = need_copy(m, bwd_copy)) return rc0;
@@ -745,15 +780,13 @@ int stage_z(ChunkPlan &p, hipStream_t s) {
 }
 
 int stage_field(const ChunkPlan &p, bool fine_pass, hipStream_t s) {
-    MlpArgs a;
-    std::memset(&a, 0, sizeof(a));
-    a.rays = p.io->rays; a.ray_stride = p.io->ray_ch;
-    a.viewdirs = p.has_vd ? p.io->rays + 8 : nullptr; a.vd_stride = p.io->ray_ch;
+    MlpArgs a{};
+    set_inputs(a, nullptr, nullptr, p.io->rays, p.io->ray_ch, fine_pass ? p.z_f : p.z_c, p.has_vd);
     if (!fine_pass) {
-        a.z_vals = p.z_c; a.P = p.R * p.Nc; a.S = p.Nc; a.out = p.raw_c;
+        a.P = p.R * p.Nc; a.S = p.Nc; a.out = p.raw_c;
         return run_field(p.coarse, a, p.cfg->precision, s);
     }
-    a.z_vals = p.z_f; a.P = p.R * (int64_t)p.Nf; a.S = p.Nf; a.out = p.raw_f;
+    a.P = p.R * (int64_t)p.Nf; a.S = p.Nf; a.out = p.raw_f;
     return run_field(p.fm, a, p.cfg->precision, s);
 }
 

@@ -242,22 +242,23 @@ static int launch_dg(const MlpArgs &a, int n_frags_fwd, int n_tiles, int n_frags
     const size_t lds = CfgDG::RING_BYTES + (size_t)Lay::N_TILES * 16 * sizeof(float) + (size_t)CfgDG::WAVES * DG_BITS_BYTES_PER_WAVE;
     static_assert(CfgDG::RING_BYTES + Lay::N_TILES * 16 * sizeof(float) + CfgDG::WAVES * DG_BITS_BYTES_PER_WAVE <= LDS_LIMIT_BYTES, "one workgroup per CU");
     static DynamicLdsOptIn opt_in;
-    if (opt_in.ensure(reinterpret_cast<const void *>(mlp_density_grad_kernel<LX, CfgDG>), lds) != hipSuccess) return NERF_AMD_EHIP;
-    const int64_t groups = (a.P + 255) / 256;      // one 256-point tile per workgroup, like the chain kernel: no tile loop, no tickets
-    hipLaunchKernelGGL((mlp_density_grad_kernel<LX, CfgDG>), dim3((unsigned)groups), dim3(512), lds, s, a);
-    return hipGetLastError() == hipSuccess ? NERF_AMD_OK : NERF_AMD_EHIP;
+    // one 256-point tile per workgroup, like the chain kernel: no tile loop, no tickets
+    return launch_field({reinterpret_cast<const void *>(mlp_density_grad_kernel<LX, CfgDG>), &opt_in, lds, 512, 256, 0}, a, s);
 }
 
 // Shipped: multires 10 (250 VGPRs, no scratch).  The multires-15 instantiation needs the 24-slot encoding products beside
 // the chain's 128 fragment registers and spills 111 VGPRs at the 256 a wave of an 8-wave workgroup can have (DESIGN.md
 // section 8d), like the RAYG chain kernel it is made of: such models take the two-launch route.
+constexpr int DG_MULTIRES = 10;
 bool density_grad_fused_supported(int multires, int use_viewdirs, int out_ch) {
-    return !use_viewdirs && out_ch >= 1 && out_ch <= 16 && multires == 10;
+    return !use_viewdirs && family_known(multires, 0, 0) && multires == DG_MULTIRES && out_ch >= 1 && head_fits(false, out_ch);
 }
 
 int launch_density_grad(const MlpArgs &a, int multires, int n_frags_fwd, int n_tiles, int n_frags_bwd, hipStream_t s) {
-    if (multires == 10) return launch_dg<10>(a, n_frags_fwd, n_tiles, n_frags_bwd, s);
-    return NERF_AMD_EUNSUPPORTED;
+    return for_family(multires, 0, 0, [&](auto f) -> int {
+        if constexpr (f.lx == DG_MULTIRES) return launch_dg<f.lx>(a, n_frags_fwd, n_tiles, n_frags_bwd, s);
+        return NERF_AMD_EUNSUPPORTED;
+    });
 }
 
 // ---- the two element-wise helpers of the density entry points for output_linear models with more than one channel

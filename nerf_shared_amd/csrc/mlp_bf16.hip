@@ -243,10 +243,6 @@ __global__ __launch_bounds__(C::WAVES * 64, C::WAVES_PER_SIMD) void mlp_bf16_ker
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");           // no LDS-DMA may outlive the workgroup
 }
 
-// tuning knob (nerf_amd_set_tuning key 0): 0 = 16x16x32 kernel, 100+ = this file's shapes (launch_one).  Atomic: the
-// launchers of concurrent host threads read it while nerf_amd_set_tuning may write it (nerf_amd.h threading contract).
-std::atomic<int> g_variant{0};
-
 template <int LX, int LD, bool VD, class C>
 static int launch_wg(const MlpArgs &a, int n_frags_used, int n_tiles, hipStream_t s) {
     constexpr int WG_THREADS = C::WAVES * 64, WG_POINTS = C::WAVES * 32 * C::NP;
@@ -254,12 +250,7 @@ static int launch_wg(const MlpArgs &a, int n_frags_used, int n_tiles, hipStream_
     if (n_frags_used != Lay::F_END || n_tiles != Lay::N_TILES) return NERF_AMD_EINVAL;
     const size_t lds = C::RING_BYTES + (size_t)Lay::N_TILES * 32 * sizeof(float);
     static DynamicLdsOptIn opt_in;
-    if (opt_in.ensure(reinterpret_cast<const void *>(mlp_bf16_kernel<LX, LD, VD, C>), lds) != hipSuccess) return NERF_AMD_EHIP;
-    const int64_t groups = (a.P + WG_POINTS - 1) / WG_POINTS;
-    if (groups <= 0) return NERF_AMD_OK;
-    if (a.P >= (int64_t)1 << 31) return NERF_AMD_EINVAL;
-    hipLaunchKernelGGL((mlp_bf16_kernel<LX, LD, VD, C>), dim3((unsigned)groups), dim3(WG_THREADS), lds, s, a);
-    return hipGetLastError() == hipSuccess ? NERF_AMD_OK : NERF_AMD_EHIP;
+    return launch_field({reinterpret_cast<const void *>(mlp_bf16_kernel<LX, LD, VD, C>), &opt_in, lds, WG_THREADS, WG_POINTS, 0}, a, s);
 }
 
 using CfgDefault = Ctx<8, 16, 4, 8, 2>;   // 64-KiB ring, mid-block sync, 2-deep read-ahead (fastest of tools/mlp_ab.py)
@@ -281,21 +272,14 @@ static int launch_one(const MlpArgs &a, int n_frags_used, int n_tiles, hipStream
     return launch_wg<LX, LD, VD, CfgDefault>(a, n_frags_used, n_tiles, s);
 }
 
-bool mlp_bf16_supported(int multires, int multires_views, int use_viewdirs) {
-    if (use_viewdirs) return (multires == 10 && multires_views == 4) || (multires == 15 && multires_views == 6);
-    return multires == 10 || multires == 15;
-}
+// (this kernel's head tile has 32 rows: no limit on output_ch beyond the program's)
+bool mlp_bf16_supported(int multires, int multires_views, int use_viewdirs) { return family_known(multires, multires_views, use_viewdirs); }
 
 int launch_mlp_bf16(const MlpArgs &a, int multires, int multires_views, int use_viewdirs,
                     int n_frags_used, int n_tiles, hipStream_t s) {
-    if (use_viewdirs) {
-        if (multires == 10 && multires_views == 4) return launch_one<10, 4, true>(a, n_frags_used, n_tiles, s);
-        if (multires == 15 && multires_views == 6) return launch_one<15, 6, true>(a, n_frags_used, n_tiles, s);
-    } else {
-        if (multires == 10) return launch_one<10, 0, false>(a, n_frags_used, n_tiles, s);
-        if (multires == 15) return launch_one<15, 0, false>(a, n_frags_used, n_tiles, s);
-    }
-    return NERF_AMD_EUNSUPPORTED;
+    return for_family(multires, multires_views, use_viewdirs, [&](auto f) {
+        return launch_one<f.lx, f.ld, f.vd>(a, n_frags_used, n_tiles, s);
+    });
 }
 
 }  // namespace na

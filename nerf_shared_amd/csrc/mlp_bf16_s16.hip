@@ -783,38 +783,14 @@ __global__ __launch_bounds__(C::WAVES * 64, 2) void mlp_bf16_s16p_kernel(MlpArgs
     }
 }
 
-// density_grad.hip includes this file for the device templates above (NA_DEVICE_TEMPLATES_ONLY): the launchers and the
-// ticket counters below belong to this translation unit alone.
+// density_grad.hip includes this file for the device templates above (NA_DEVICE_TEMPLATES_ONLY): the launchers below
+// belong to this translation unit alone.
 #ifndef NA_DEVICE_TEMPLATES_ONLY
-// ---- {ticket, done} pairs of the dynamic deal
-namespace {
-constexpr int TILE_CTR_SLOTS = 1024;
-unsigned *g_tile_ctr[16] = {};
-std::atomic<unsigned> g_tile_ctr_next{0};
-}  // namespace
-
-int tile_counters_init(int device) {
-    if (device < 0 || device >= 16) return NERF_AMD_EINVAL;
-    if (g_tile_ctr[device]) return NERF_AMD_OK;
-    unsigned *p = nullptr;
-    if (hipMalloc(reinterpret_cast<void **>(&p), TILE_CTR_SLOTS * 2 * sizeof(unsigned)) != hipSuccess) return NERF_AMD_EHIP;
-    if (hipMemset(p, 0, TILE_CTR_SLOTS * 2 * sizeof(unsigned)) != hipSuccess) { (void)hipFree(p); return NERF_AMD_EHIP; }
-    g_tile_ctr[device] = p;
-    return NERF_AMD_OK;
-}
-
-unsigned *tile_counter_slot(int device) {
-    if (device < 0 || device >= 16 || !g_tile_ctr[device]) return nullptr;
-    return g_tile_ctr[device] + 2 * (g_tile_ctr_next.fetch_add(1, std::memory_order_relaxed) % TILE_CTR_SLOTS);
-}
-
-unsigned *tile_counter_for(bool deal, hipStream_t s) {
-    if (!deal) return nullptr;
-    hipStreamCaptureStatus st = hipStreamCaptureStatusNone;
-    if (hipStreamIsCapturing(s, &st) != hipSuccess || st != hipStreamCaptureStatusNone) return nullptr;
-    int dev = 0;
-    return hipGetDevice(&dev) == hipSuccess ? tile_counter_slot(dev) : nullptr;
-}
+#ifdef NERF_AMD_STAMPS
+static MlpArgs stamped(MlpArgs a) { a.stamps = g_stamp_buf; return a; }
+#else
+static const MlpArgs &stamped(const MlpArgs &a) { return a; }
+#endif
 
 template <int LX, int LD, bool VD, class C>
 static int launch_wg16p(const MlpArgs &a, int n_frags_used, int n_tiles, hipStream_t s) {
@@ -823,20 +799,9 @@ static int launch_wg16p(const MlpArgs &a, int n_frags_used, int n_tiles, hipStre
     if (n_frags_used != Lay::F_END || n_tiles != Lay::N_TILES) return NERF_AMD_EINVAL;
     const size_t lds = C::RING_BYTES + (size_t)Lay::N_TILES * 16 * sizeof(float) + 16;      // + the ticket word
     static DynamicLdsOptIn opt_in;
-    if (opt_in.ensure(reinterpret_cast<const void *>(mlp_bf16_s16p_kernel<LX, LD, VD, C>), lds) != hipSuccess) return NERF_AMD_EHIP;
-    int64_t groups = (a.P + WG_POINTS - 1) / WG_POINTS;
-    if (groups <= 0) return NERF_AMD_OK;
-    if (a.P >= (int64_t)1 << 31) return NERF_AMD_EINVAL;
-    const int n_cu = device_cu_count();      // one workgroup per CU walks the tiles
-    const bool deal = groups > 2 * (int64_t)n_cu && g_variant != 42;      // more than two tiles per workgroup: dealt by ticket (A/B 42: static)
-    if (groups > n_cu) groups = n_cu;
-    MlpArgs a2 = a;
-    a2.tile_ctr = tile_counter_for(deal, s);
-#ifdef NERF_AMD_STAMPS
-    a2.stamps = g_stamp_buf;
-#endif
-    hipLaunchKernelGGL((mlp_bf16_s16p_kernel<LX, LD, VD, C>), dim3((unsigned)groups), dim3(WG_THREADS), lds, s, a2);
-    return hipGetLastError() == hipSuccess ? NERF_AMD_OK : NERF_AMD_EHIP;
+    // one workgroup per CU walks the tiles
+    return launch_field({reinterpret_cast<const void *>(mlp_bf16_s16p_kernel<LX, LD, VD, C>), &opt_in, lds, WG_THREADS, WG_POINTS, 1},
+                        stamped(a), s);
 }
 
 template <int LX, int LD, bool VD, class C, bool SAVE = false>
@@ -846,24 +811,10 @@ static int launch_wg16(const MlpArgs &a, int n_frags_used, int n_tiles, hipStrea
     if (n_frags_used != Lay::F_END || n_tiles != Lay::N_TILES) return NERF_AMD_EINVAL;
     const size_t lds = C::RING_BYTES + (size_t)Lay::N_TILES * 16 * sizeof(float) + 16;      // + the ticket word
     static DynamicLdsOptIn opt_in;         // per kernel instantiation, tracks every device (launch_util.h)
-    if (opt_in.ensure(reinterpret_cast<const void *>(mlp_bf16_s16_kernel<LX, LD, VD, C, SAVE>), lds) != hipSuccess)
-        return NERF_AMD_EHIP;
-    int64_t groups = (a.P + WG_POINTS - 1) / WG_POINTS;
-    if (groups <= 0) return NERF_AMD_OK;
-    if (a.P >= (int64_t)1 << 31) return NERF_AMD_EINVAL;
-    bool deal = false;
-    if (g_variant != 31) {                 // one workgroup per CU walks the tiles (+1 %: no per-tile dispatch); 31 = A/B off
-        const int n_wg = device_cu_count() * (8 / C::WAVES);     // 4-wave workgroups: two per CU
-        deal = groups > 2 * (int64_t)n_wg && g_variant != 42;    // ... and takes them by ticket (A/B 42: blockIdx + k gridDim)
-        if (groups > n_wg) groups = n_wg;
-    }
-    MlpArgs a2 = a;
-    a2.tile_ctr = tile_counter_for(deal, s);
-#ifdef NERF_AMD_STAMPS
-    a2.stamps = g_stamp_buf;
-#endif
-    hipLaunchKernelGGL((mlp_bf16_s16_kernel<LX, LD, VD, C, SAVE>), dim3((unsigned)groups), dim3(WG_THREADS), lds, s, a2);
-    return hipGetLastError() == hipSuccess ? NERF_AMD_OK : NERF_AMD_EHIP;
+    // one workgroup per CU walks the tiles (+1 %: no per-tile dispatch; 4-wave workgroups: two per CU); 31 = A/B off
+    const int wg_per_cu = g_variant != 31 ? 8 / C::WAVES : 0;
+    return launch_field({reinterpret_cast<const void *>(mlp_bf16_s16_kernel<LX, LD, VD, C, SAVE>), &opt_in, lds, WG_THREADS, WG_POINTS,
+                         wg_per_cu}, stamped(a), s);
 }
 
 // 64-KiB ring of 16-fragment blocks, mid-block sync, 4-deep read-ahead pinned in front of the MFMAs it runs ahead of
@@ -890,25 +841,13 @@ int launch_mlp_bf16_s16(const MlpArgs &a, int multires, int multires_views, int 
         if (experiment_launch_s16(a, multires, multires_views, use_viewdirs, n_frags_used, n_tiles, s, &rc_x)) return rc_x;
     }
 #endif
-    if (use_viewdirs && multires == 10 && multires_views == 4 && g_variant == 40) return launch_wg16<10, 4, true, Cfg16R1>(a, n_frags_used, n_tiles, s);
-    if (g_variant != 41) {                  // 41 = A/B: the simple per-tile kernel
-        if (use_viewdirs) {
-            if (multires == 10 && multires_views == 4) return launch_wg16p<10, 4, true, Cfg16P>(a, n_frags_used, n_tiles, s);
-            if (multires == 15 && multires_views == 6) return launch_wg16p<15, 6, true, Cfg16P>(a, n_frags_used, n_tiles, s);
-        } else if (a.out_ch <= 16) {
-            if (multires == 10) return launch_wg16p<10, 0, false, Cfg16P>(a, n_frags_used, n_tiles, s);
-            if (multires == 15) return launch_wg16p<15, 0, false, Cfg16P>(a, n_frags_used, n_tiles, s);
-        }
-        return NERF_AMD_EUNSUPPORTED;
-    }
-    if (use_viewdirs) {
-        if (multires == 10 && multires_views == 4) return launch_wg16<10, 4, true, Cfg16>(a, n_frags_used, n_tiles, s);
-        if (multires == 15 && multires_views == 6) return launch_wg16<15, 6, true, Cfg16>(a, n_frags_used, n_tiles, s);
-    } else if (a.out_ch <= 16) {
-        if (multires == 10) return launch_wg16<10, 0, false, Cfg16>(a, n_frags_used, n_tiles, s);
-        if (multires == 15) return launch_wg16<15, 0, false, Cfg16>(a, n_frags_used, n_tiles, s);
-    }
-    return NERF_AMD_EUNSUPPORTED;
+    return for_family(multires, multires_views, use_viewdirs, [&](auto f) -> int {
+        if (!head_fits(f.vd, a.out_ch)) return NERF_AMD_EUNSUPPORTED;
+        if constexpr (f.lx == 10 && f.ld == 4 && f.vd)
+            if (g_variant == 40) return launch_wg16<10, 4, true, Cfg16R1>(a, n_frags_used, n_tiles, s);
+        if (g_variant != 41) return launch_wg16p<f.lx, f.ld, f.vd, Cfg16P>(a, n_frags_used, n_tiles, s);
+        return launch_wg16<f.lx, f.ld, f.vd, Cfg16>(a, n_frags_used, n_tiles, s);       // 41 = A/B: the simple per-tile kernel
+    });
 }
 
 #ifdef NERF_AMD_STAMPS
@@ -918,15 +857,12 @@ extern "C" void nerf_amd_debug_set_stamp_buffer(void *p) { g_stamp_buf = static_
 int launch_mlp_bf16_s16_save(const MlpArgs &a, int multires, int multires_views, int use_viewdirs, int n_frags_used, int n_tiles,
                              hipStream_t s) {
     // the training forward keeps the round-1 pipeline shape: with its activation stores the pinned / split shape spills
-    if (use_viewdirs) {
-        if (multires == 10 && multires_views == 4) return launch_wg16<10, 4, true, CfgSaveT<10, 4>, true>(a, n_frags_used, n_tiles, s);
-        if (multires == 15 && multires_views == 6) return launch_wg16<15, 6, true, CfgSaveT<15, 6>, true>(a, n_frags_used, n_tiles, s);
-    } else if (a.out_ch <= 16) {             // output_linear models (nerf.py:91-94): hidden layers saved the same way, no view branch
-        using CfgSaveNV = Ctx<8, 16, 4, 8, 2>;
-        if (multires == 10) return launch_wg16<10, 0, false, CfgSaveNV, true>(a, n_frags_used, n_tiles, s);
-        if (multires == 15) return launch_wg16<15, 0, false, CfgSaveNV, true>(a, n_frags_used, n_tiles, s);
-    }
-    return NERF_AMD_EUNSUPPORTED;
+    return for_family(multires, multires_views, use_viewdirs, [&](auto f) -> int {
+        if (!head_fits(f.vd, a.out_ch)) return NERF_AMD_EUNSUPPORTED;
+        // output_linear models (nerf.py:91-94): hidden layers saved the same way, no view branch
+        using Cfg = std::conditional_t<f.vd, CfgSaveT<f.lx, f.ld>, Ctx<8, 16, 4, 8, 2>>;
+        return launch_wg16<f.lx, f.ld, f.vd, Cfg, true>(a, n_frags_used, n_tiles, s);
+    });
 }
 
 #endif  // NA_DEVICE_TEMPLATES_ONLY

@@ -405,13 +405,9 @@ static int launch_bwd_as(const MlpArgs &a, int n_frags_used, hipStream_t s) {
     if (n_frags_used != LayoutB<KE, KD, VD>::F_END) return NERF_AMD_EINVAL;
     if (a.P <= 0) return NERF_AMD_OK;
     if (a.P >= (int64_t)1 << 31) return NERF_AMD_EINVAL;
-    if (!VD && a.out_ch > 16) return NERF_AMD_EUNSUPPORTED;
-    const size_t lds = C::RING_BYTES;
+    if (!head_fits(VD, a.out_ch)) return NERF_AMD_EUNSUPPORTED;
     static DynamicLdsOptIn opt_in;
-    if (opt_in.ensure(reinterpret_cast<const void *>(mlp_bwd_s16_kernel<LX, LD, VD, C, RAYG>), lds) != hipSuccess) return NERF_AMD_EHIP;
-    const int64_t groups = (a.P + 255) / 256;
-    hipLaunchKernelGGL((mlp_bwd_s16_kernel<LX, LD, VD, C, RAYG>), dim3((unsigned)groups), dim3(512), lds, s, a);
-    return hipGetLastError() == hipSuccess ? NERF_AMD_OK : NERF_AMD_EHIP;
+    return launch_field({reinterpret_cast<const void *>(mlp_bwd_s16_kernel<LX, LD, VD, C, RAYG>), &opt_in, C::RING_BYTES, 512, 256, 0}, a, s);
 }
 
 template <int LX, int LD, bool VD>
@@ -422,14 +418,7 @@ static int launch_bwd(const MlpArgs &a, int n_frags_used, hipStream_t s) {
 }
 
 int launch_mlp_bwd_s16(const MlpArgs &a, int multires, int multires_views, int use_viewdirs, int n_frags_used, hipStream_t s) {
-    if (use_viewdirs) {
-        if (multires == 10 && multires_views == 4) return launch_bwd<10, 4, true>(a, n_frags_used, s);
-        if (multires == 15 && multires_views == 6) return launch_bwd<15, 6, true>(a, n_frags_used, s);
-    } else {
-        if (multires == 10) return launch_bwd<10, 0, false>(a, n_frags_used, s);
-        if (multires == 15) return launch_bwd<15, 0, false>(a, n_frags_used, s);
-    }
-    return NERF_AMD_EUNSUPPORTED;
+    return for_family(multires, multires_views, use_viewdirs, [&](auto f) { return launch_bwd<f.lx, f.ld, f.vd>(a, n_frags_used, s); });
 }
 
 #endif  // NA_DEVICE_TEMPLATES_ONLY

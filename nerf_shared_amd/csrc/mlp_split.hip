@@ -362,17 +362,8 @@ static int launch_split(const MlpArgs &a, int n_frags_used, int n_tiles, hipStre
     if (n_frags_used != Lay::F_END || n_tiles != Lay::N_TILES) return NERF_AMD_EINVAL;
     const size_t lds = C::RING_BYTES + (size_t)Lay::N_TILES * 16 * sizeof(float) + 16;      // + the ticket word
     static DynamicLdsOptIn opt_in;         // per kernel instantiation, tracks every device (launch_util.h)
-    if (opt_in.ensure(reinterpret_cast<const void *>(mlp_split_kernel<LX, LD, VD, C, SAVE>), lds) != hipSuccess) return NERF_AMD_EHIP;
-    int64_t groups = (a.P + WG_POINTS - 1) / WG_POINTS;
-    if (groups <= 0) return NERF_AMD_OK;
-    if (a.P >= (int64_t)1 << 31) return NERF_AMD_EINVAL;
-    const int n_wg = device_cu_count();      // one workgroup per CU walks the tiles
-    const bool deal = groups > 2 * (int64_t)n_wg && g_variant != 42;      // dealt by ticket (A/B 42: blockIdx + k gridDim)
-    if (groups > n_wg) groups = n_wg;
-    MlpArgs a2 = a;
-    a2.tile_ctr = tile_counter_for(deal, s);
-    hipLaunchKernelGGL((mlp_split_kernel<LX, LD, VD, C, SAVE>), dim3((unsigned)groups), dim3(WG_THREADS), lds, s, a2);
-    return hipGetLastError() == hipSuccess ? NERF_AMD_OK : NERF_AMD_EHIP;
+    // one workgroup per CU walks the tiles
+    return launch_field({reinterpret_cast<const void *>(mlp_split_kernel<LX, LD, VD, C, SAVE>), &opt_in, lds, WG_THREADS, WG_POINTS, 1}, a, s);
 }
 
 // the pipeline shape of the bf16 kernel (mlp_bf16_s16.hip Cfg16): 64-KiB ring of 16-fragment blocks, mid-block sync,
@@ -380,20 +371,15 @@ static int launch_split(const MlpArgs &a, int n_frags_used, int n_tiles, hipStre
 using CfgSplit = Ctx<8, 16, 4, 8, 4, 0, 1, 4 + 8 + 64>;
 
 bool mlp_split_supported(int multires, int multires_views, int use_viewdirs, int out_ch) {
-    if (use_viewdirs) return (multires == 10 && multires_views == 4) || (multires == 15 && multires_views == 6);
-    return out_ch <= 16 && (multires == 10 || multires == 15);
+    return family_known(multires, multires_views, use_viewdirs) && head_fits(use_viewdirs, out_ch);
 }
 
 int launch_mlp_split(const MlpArgs &a, int multires, int multires_views, int use_viewdirs, int n_frags_used, int n_tiles,
                      hipStream_t s) {
-    if (use_viewdirs) {
-        if (multires == 10 && multires_views == 4) return launch_split<10, 4, true, CfgSplit>(a, n_frags_used, n_tiles, s);
-        if (multires == 15 && multires_views == 6) return launch_split<15, 6, true, CfgSplit>(a, n_frags_used, n_tiles, s);
-    } else if (a.out_ch <= 16) {
-        if (multires == 10) return launch_split<10, 0, false, CfgSplit>(a, n_frags_used, n_tiles, s);
-        if (multires == 15) return launch_split<15, 0, false, CfgSplit>(a, n_frags_used, n_tiles, s);
-    }
-    return NERF_AMD_EUNSUPPORTED;
+    return for_family(multires, multires_views, use_viewdirs, [&](auto f) -> int {
+        if (!head_fits(f.vd, a.out_ch)) return NERF_AMD_EUNSUPPORTED;
+        return launch_split<f.lx, f.ld, f.vd, CfgSplit>(a, n_frags_used, n_tiles, s);
+    });
 }
 
 // The training forward of the split-precision mode: the same kernel, every layer's (hi, lo) output saved (kernels.h).
@@ -401,14 +387,10 @@ using CfgSplitSave = Ctx<8, 16, 4, 8, 2>;     // the plain pipeline shape, like 
 
 int launch_mlp_split_save(const MlpArgs &a, int multires, int multires_views, int use_viewdirs, int n_frags_used, int n_tiles,
                           hipStream_t s) {
-    if (use_viewdirs) {
-        if (multires == 10 && multires_views == 4) return launch_split<10, 4, true, CfgSplitSave, true>(a, n_frags_used, n_tiles, s);
-        if (multires == 15 && multires_views == 6) return launch_split<15, 6, true, CfgSplitSave, true>(a, n_frags_used, n_tiles, s);
-    } else if (a.out_ch <= 16) {
-        if (multires == 10) return launch_split<10, 0, false, CfgSplitSave, true>(a, n_frags_used, n_tiles, s);
-        if (multires == 15) return launch_split<15, 0, false, CfgSplitSave, true>(a, n_frags_used, n_tiles, s);
-    }
-    return NERF_AMD_EUNSUPPORTED;
+    return for_family(multires, multires_views, use_viewdirs, [&](auto f) -> int {
+        if (!head_fits(f.vd, a.out_ch)) return NERF_AMD_EUNSUPPORTED;
+        return launch_split<f.lx, f.ld, f.vd, CfgSplitSave, true>(a, n_frags_used, n_tiles, s);
+    });
 }
 
 }  // namespace na

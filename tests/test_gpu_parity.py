@@ -328,6 +328,67 @@ def test_pipelined_kernel_equals_per_tile_kernel_on_many_shapes(dev):
         _lib.lib.nerf_amd_set_tuning(0, 0)
 
 
+# What the fused kernels cover for NeRF(D=8, W=256, skips=[4]), written out by hand -- not asked of the library:
+#   families (multires, multires_views) = (10, 4), (15, 6) with view branch; multires 10, 15 without (views ignored);
+#   b  bf16 inference: every family member (the first-generation kernel takes any output_ch)
+#   s  split-precision inference, t  fused training in bf16 and in fp32_split: family, output_ch <= 16 without view branch
+#   d  fused density value + gradient kernel: no view branch, multires 10, output_ch <= 16
+#   exact-fp32 training: every architecture.
+# One row per (multires, multires_views, use_viewdirs): the letters for output_ch 4, 5, 16, 17.
+FAMILY_COVERAGE = {
+    (5, 4, 0): ("", "", "", ""),               (5, 4, 1): ("", "", "", ""),
+    (5, 6, 0): ("", "", "", ""),               (5, 6, 1): ("", "", "", ""),
+    (10, 4, 0): ("bstd", "bstd", "bstd", "b"), (10, 4, 1): ("bst", "bst", "bst", "bst"),
+    (10, 6, 0): ("bstd", "bstd", "bstd", "b"), (10, 6, 1): ("", "", "", ""),
+    (15, 4, 0): ("bst", "bst", "bst", "b"),    (15, 4, 1): ("", "", "", ""),
+    (15, 6, 0): ("bst", "bst", "bst", "b"),    (15, 6, 1): ("bst", "bst", "bst", "bst"),
+}
+
+
+def test_family_coverage_is_what_it_was(dev):
+    """The support predicates of the C ABI against the hand-written table above, the refusal of a bf16 forward outside
+    the family (code and message), and the output_ch = 17 model that bf16 inference serves on the first-generation kernel."""
+    import ctypes
+    from nerf_shared_amd import _lib
+    lib = _lib.lib
+    with torch.cuda.device(dev):
+        for (multires, views, vd), per_och in sorted(FAMILY_COVERAGE.items()):
+            for och, want in zip((4, 5, 16, 17), per_och):
+                arch = _lib.make_arch(8, 256, och, [4], vd, multires, views, 0)
+                h = ctypes.c_void_p()
+                _lib.check(lib.nerf_amd_model_create(ctypes.byref(arch), dev.index or 0, ctypes.byref(h)), "nerf_amd_model_create")
+                try:
+                    got = {"b": lib.nerf_amd_model_supports_bf16(h), "s": lib.nerf_amd_model_supports_split(h),
+                           "t": lib.nerf_amd_model_supports_training(h, _lib.PREC_BF16),
+                           "t_split": lib.nerf_amd_model_supports_training(h, _lib.PREC_FP32_SPLIT),
+                           "t_fp32": lib.nerf_amd_model_supports_training(h, _lib.PREC_FP32),
+                           "d": lib.nerf_amd_density_grad_fused(h, _lib.PREC_BF16)}
+                finally:
+                    lib.nerf_amd_model_destroy(h)
+                expect = {"b": int("b" in want), "s": int("s" in want), "t": int("t" in want), "t_split": int("t" in want),
+                          "t_fp32": 1, "d": int("d" in want)}
+                assert got == expect, (multires, views, vd, och)
+    # outside the family: refused, in the words the library has always used
+    rng = np.random.default_rng(5)
+    pts = torch.from_numpy(rng.uniform(-3, 3, size=(257, 1, 3)).astype(np.float32)).to(dev)
+    vdirs = torch.nn.functional.normalize(torch.from_numpy(rng.normal(size=(257, 3)).astype(np.float32)), dim=-1).to(dev)
+    m = gpu_model(dev, 3, 3.0, "fp32", **dict(VD, multires=5))
+    handle = m._model_handle(dev, _lib.COPY_BF16)
+    out = torch.empty(257, 4, device=dev)
+    with torch.cuda.device(dev):
+        rc = lib.nerf_amd_nerf_forward(handle, pts.data_ptr(), vdirs.data_ptr(), 257, 1, out.data_ptr(), _lib.PREC_BF16, _lib.stream_of(dev))
+    assert rc == -3                                                # NERF_AMD_EUNSUPPORTED
+    assert lib.nerf_amd_last_error().decode() == ("fused bf16 kernel needs D=8, W=256, skips=[4], multires/views in {(10,4),(15,6)}; "
+                                                  "use NERF_AMD_PREC_FP32")
+    # 17 channels without view branch: one more than the 16x16x32 kernels' head tile holds; bf16 still runs (32x32x16 kernel)
+    wide = dict(NOVD, output_ch=17)
+    mb, mf = gpu_model(dev, 2, 3.0, "bf16", **wide), gpu_model(dev, 2, 3.0, "fp32", **wide)
+    assert mb.supports_bf16() and mb._precision_code() == _lib.PREC_BF16
+    got, ref = mb(pts, None), mf(pts, None)
+    assert got.shape == (257, 1, 17)
+    assert rel_l2(got, ref) < 3e-2
+
+
 def test_weight_update_repacks(dev, golden):
     g = golden("g2_nerf")
     pts, vd = torch.from_numpy(g["pts"]).to(dev), torch.from_numpy(g["viewdirs"]).to(dev)

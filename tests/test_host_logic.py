@@ -330,6 +330,56 @@ def test_field_kernel_keeps_its_weight_read_ahead(tmp_path):
             assert not check_vmcnt.check(asm, tag, verbose=False, lag=lag, slack=3)["ok"]      # the checker can fail
 
 
+_ISA_DIFF_ASM = """\t.text
+_Z1aPf:                                 ; @_Z1aPf
+; %%bb.0:
+\ts_load_dwordx2 s[0:1], s[4:5], 0x0
+\ts_cbranch_scc1 .LBB%(n)d_2
+.LBB%(n)d_2:
+\tv_mov_b32_e32 v0, %(imm)s             ; a comment
+\ts_endpgm
+.Lfunc_end0:
+%(second)s\t.amdgpu_metadata
+---
+amdhsa.kernels:
+  - .group_segment_fixed_size: 0
+    .name:           _Z1aPf
+    .private_segment_fixed_size: 0
+    .sgpr_count:     8
+    .vgpr_count:     %(vgprs)d
+    .vgpr_spill_count: 0
+%(second_meta)s...
+\t.end_amdgpu_metadata
+"""
+_ISA_DIFF_B = "_Z1bPf:\n\ts_endpgm\n.Lfunc_end1:\n"
+_ISA_DIFF_B_META = ("  - .group_segment_fixed_size: 0\n    .name:           _Z1bPf\n    .private_segment_fixed_size: 0\n"
+                    "    .sgpr_count:     8\n    .vgpr_count:     1\n    .vgpr_spill_count: 0\n")
+
+
+def test_isa_diff_tells_equal_changed_and_missing(tmp_path, capsys):
+    """tools/isa_diff.py on hand-written assembly: equal streams (labels renumbered, comments moved) pass; one changed
+    instruction, one changed register count and a missing kernel each fail and name the symbol."""
+    sys.path.insert(0, os.path.join(REPO, "tools"))
+    import isa_diff
+    base = dict(n=0, imm="1", vgprs=4, second=_ISA_DIFF_B, second_meta=_ISA_DIFF_B_META)
+
+    def run(**change):
+        for side, kw in (("a", base), ("b", dict(base, **change))):
+            os.makedirs(tmp_path / side, exist_ok=True)
+            (tmp_path / side / "unit.s").write_text(_ISA_DIFF_ASM % kw)
+        rc = isa_diff.main(str(tmp_path / "a"), str(tmp_path / "b"))
+        return rc, capsys.readouterr().out
+
+    rc, out = run(n=7)                                   # the same code under other label numbers
+    assert rc == 0 and "IDENTICAL" in out
+    rc, out = run(imm="2")
+    assert rc != 0 and "_Z1aPf: instructions differ" in out and "_Z1bPf:" not in out
+    rc, out = run(vgprs=5)
+    assert rc != 0 and "_Z1aPf: .vgpr_count 4 vs 5" in out
+    rc, out = run(second="", second_meta="")
+    assert rc != 0 and "_Z1bPf: only in A" in out and "_Z1aPf:" not in out
+
+
 def test_bench_reports_traffic_only_for_the_build_it_was_measured_on(tmp_path, monkeypatch):
     """bench.py's roofline.traffic comes from a profiles/ PMC summary; it must not survive a kernel change."""
     sys.path.insert(0, REPO)
