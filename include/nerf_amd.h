@@ -507,6 +507,7 @@ int nerf_amd_adam_step_device(int32_t n, float *const *params, const float *cons
 int nerf_amd_profile_enable(int on);
 /* Tuning knobs for A/B measurements (results are identical for every setting).
  * key 0: weight-pipeline shape of the fused bf16 kernel (0 = default; see mlp_bf16.hip launch_one).
+ *        Values 50..58 once chose earlier generations of the weight-gradient launcher; they are still accepted and do nothing.
  * key 1: route of nerf_amd_density_value_grad (0 = default: the fused kernel where it covers the model, 1 = always two launches). */
 int nerf_amd_set_tuning(int key, int value);
 int nerf_amd_profile_collect(int64_t launches[3], double total_ms[3], double total_points[3]);

@@ -53,13 +53,15 @@ WEIGHT_SEED = {name: 100 + i for i, name in enumerate(ARCHS)}
 # (rays, samples) of every training case: the awkward counts of tests/test_gpu_fuzz.py (one point, the 32-point chunks
 # of the weight-gradient products, the 256-point tiles, ragged tails), plus one count just past each boundary at which
 # a launcher changes shape:
-#   481   csrc/backward.hip DwSeq::flush / train_param_grads_split: a product gets n_chunks / 8 workgroups, so the 16th
+#   481   csrc/dw_plan.h DwPlan::layout (both precisions): a job gets at most n_chunks / 8 workgroups, so the 16th
 #         32-point chunk (point 481) brings the second workgroup and the second slab to reduce; from there on every
 #         workgroup streams more chunks than one (the strided chunk loop of dw2_body / dw2s_body)
 #   1025  csrc/train_f32.hip dw_slice_pts: 1024 points per weight-gradient slice, so the second slice (blockIdx.y = 1)
-#   5633  backward.hip dw_share_workgroups, view-branch model (12 products): up to 21 workgroups per product the cap
-#         n_chunks / 8 decides the split of the 256 workgroups, from 22 (n_chunks >= 176) the cost table does
-#   7500  the same for the output_linear model (9 products: cap 29, n_chunks >= 232)
+#   5633  dw_plan.h dw_share_workgroups (tools/dw_plan_check.cpp prints the shares).  View-branch model, 13 jobs, cap
+#         n_chunks / 8 = 22: the 256 workgroups run out, the wide jobs sit at the cap and the cost table deals the rest
+#         (bf16: 19 22 22 22 22 18 22 22 22 22 22 12 9).  The output_linear model's 9 jobs all sit at the cap: 198
+#   7500  cap 29: the output_linear model's workgroups run out too (27 29 29 29 29 26 29 29 29), and the view-branch
+#         model has the shares of a full-size step, which the cap no longer touches (15 24 24 24 24 14 24 24 24 26 17 9 7)
 #   (257 -- second row of dw_small_kernel's 256-point grid, second tile of the dX chain -- is in the fuzz list; the
 #   1024-workgroup cap of launch_dw_small and the 32768-slice cap of dw_slice_pts lie beyond 2.6e5 points, where the
 #   2^24 precondition no longer holds)

@@ -380,6 +380,13 @@ def test_isa_diff_tells_equal_changed_and_missing(tmp_path, capsys):
     assert rc != 0 and "_Z1bPf: only in A" in out and "_Z1aPf:" not in out
 
 
+def test_weight_gradient_launcher_has_one_path():
+    """csrc/backward.hip launches the weight gradients one way: it does not read the A/B selector of
+    nerf_amd_set_tuning key 0 (g_variant; its values 50..58 once chose earlier generations of that launcher)."""
+    src = open(os.path.join(REPO, "nerf_shared_amd", "csrc", "backward.hip")).read()
+    assert "g_variant" not in src
+
+
 def test_bench_reports_traffic_only_for_the_build_it_was_measured_on(tmp_path, monkeypatch):
     """bench.py's roofline.traffic comes from a profiles/ PMC summary; it must not survive a kernel change."""
     sys.path.insert(0, REPO)

@@ -2,10 +2,13 @@
 """When did each workgroup of the weight-gradient launch start and end?  (GPU box, scratch build)
 
     make -C nerf_shared_amd/csrc OUT=../../scratch_libs/libstamps.so OBJDIR=build_stamps EXTRA=-DNERF_AMD_X_DW_STAMPS
-    NERF_AMD_LIB=$PWD/scratch_libs/libstamps.so python tools/micro/dw_stamps.py [--tuning 63]
+    NERF_AMD_LIB=$PWD/scratch_libs/libstamps.so python tools/micro/dw_stamps.py [--precision fp32_split]
 
-Runs a few 1024-ray training steps (tools/train_bench.py's) and prints, for the LAST dw_multi_kernel launch (the coarse
-network's 65536 points), per product: workgroups, their XCDs, first start / last end, spread of the ends (us).
+Runs a few 1024-ray training steps (tools/train_bench.py's) and prints, for the LAST dw_multi_kernel (or, in split
+precision, dw_multi_split_kernel) launch (the coarse network's 65536 points), per job of the plan (csrc/dw_plan.h): workgroups,
+their XCDs, first start / last end, spread of the ends (us).  The us per chunk it prints are what the cost columns of
+dw_plan.h's shape table were measured with.  --tuning sets an A/B value of nerf_amd_set_tuning key 0 for the other kernels of
+the step; the weight-gradient launch itself has no variants (50..58 chose earlier generations of it and do nothing now).
 """
 import argparse
 import ctypes
@@ -24,7 +27,7 @@ ARCH = dict(D=8, W=256, output_ch=5, skips=[4], use_viewdirs=True, multires=10, 
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--tuning", type=int, default=0)
+    ap.add_argument("--tuning", type=int, default=0, help="nerf_amd_set_tuning(0, value) for the rest of the step")
     ap.add_argument("--rays", type=int, default=1024)
     ap.add_argument("--coarse-only", type=int, default=0, metavar="N_SAMPLES", help="N_importance 0: the stamped launch is this many samples per ray")
     ap.add_argument("--rgb0", action="store_true", help="the loss includes the coarse image (main.py:93-98): the stamped launch is the coarse network's, inside the full step")

@@ -94,7 +94,8 @@ __global__ __launch_bounds__(512, 2) void stream_kernel(const char *A, const cha
     if (acc == 123.456f) sink[0] = acc;
 }
 
-// The one-launch path of backward.hip (DwSeq::flush): J products, each with its own pair of row arrays, ~256 / J workgroups
+// The one-launch path of backward.hip (DwSeq::flush when this was measured; since then csrc/dw_plan.h DwPlan::layout -- the
+// label below keeps the old name so that new output lines up with profiles/r04_dw_stream_micro.txt): J products, each with its own pair of row arrays, ~256 / J workgroups
 // per product reading chunks wg, wg + nb, ...: J x 2 windows of nb x 16 KiB that advance in lockstep, the arrays
 // n_chunks x 16 KiB apart.  rot: product j starts at chunk j n / J and wraps; skew: the arrays are skew bytes further apart
 template <int NS>

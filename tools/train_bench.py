@@ -27,7 +27,7 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--adam", choices=["foreach", "fused", "amd"], default="amd",
                     help="amd: nerf_shared_amd.optim.Adam (what utils.get_optimizer returns); foreach / fused: torch.optim.Adam")
-    ap.add_argument("--tuning", type=int, default=0, help="nerf_amd_set_tuning(0, value): 50 = round-1 weight-gradient kernel")
+    ap.add_argument("--tuning", type=int, default=0, help="nerf_amd_set_tuning(0, value): an A/B value of include/nerf_amd.h key 0 (50..58, the weight-gradient launchers of rounds 1-3, do nothing any more)")
     ap.add_argument("--precision", choices=["bf16", "fp32_split", "fp32"], default="bf16",
                     help="arithmetic of the field and of its backward pass (fp32 trains on the exact-fp32 path, csrc/train_f32.hip)")
     ap.add_argument("--netdepth", type=int, default=8, help="anything but 8 x 256 with skip 4 trains on the exact-fp32 path (csrc/train_f32.hip)")
