@@ -108,6 +108,14 @@ int  nerf_amd_model_update(nerf_amd_model *m, const float *const *weights, const
 #define NERF_AMD_COPY_FP32      16  /* fp32 fragment stream + biases: NERF_AMD_PREC_FP32 (inference and training forward), nerf_amd_mlp_embedded */
 #define NERF_AMD_COPY_FP32_BWD  32  /* transposed fp32 stream: nerf_amd_field_backward in NERF_AMD_PREC_FP32 */
 #define NERF_AMD_COPY_ALL       63
+/* The folded bf16 stream of a view-branch model: feature_linear has no activation behind it, so the bf16 render kernels
+ * evaluate views_linears.0 on h8 directly through W' = Wv[:, :W] . Wf and b' = Wv[:, :W] . bf + bv, formed in fp32 from the
+ * fp32 parameters and rounded to bf16 once (10.9 % fewer MFMAs per point; sigma is bit-identical, rgb moves by less than the
+ * mode's own error).  It is NOT part of NERF_AMD_COPY_ALL: it is packed only when this bit is given (two small launches of
+ * its own), so a training step packs exactly what it packed before.  nerf_amd_render_batch runs the folded stream when this
+ * copy holds the current parameters and the unfolded one otherwise (nerf_amd_set_tuning key 2).  Ignored for models that
+ * have nothing to fold (no view branch, or outside the fused family). */
+#define NERF_AMD_COPY_BF16_FOLD 128
 int  nerf_amd_model_update_copies(nerf_amd_model *m, const float *const *weights, const float *const *biases,
                                   int n_tensors, int copies, int others_current, void *stream);
 void nerf_amd_model_destroy(nerf_amd_model *m);
@@ -122,7 +130,8 @@ int  nerf_amd_model_out_ch(const nerf_amd_model *m);       /* 4 with viewdirs, e
  * pointers here.  `stream_out` receives n_frags*512 uint16 (bf16 bits) and
  * `bias_out` the fp32 bias table; pass NULL to query sizes only. */
 int  nerf_amd_pack_bf16_host(const nerf_amd_arch *arch, int shape /* 32: 32x32x16 stream, 16: 16x16x32 stream, 17: transposed
-                                (backward) stream, 18 / 19: the split-precision forward / transposed streams (fp16 hi, lo fragments) */,
+                                (backward) stream, 18 / 19: the split-precision forward / transposed streams (fp16 hi, lo fragments),
+                                20: the folded 16x16x32 stream of a view-branch model (NERF_AMD_COPY_BF16_FOLD) */,
                              const float *const *weights,
                              const float *const *biases, int n_tensors,
                              uint16_t *stream_out, int64_t *n_frags, float *bias_out, int64_t *n_bias);
@@ -508,7 +517,12 @@ int nerf_amd_profile_enable(int on);
 /* Tuning knobs for A/B measurements (results are identical for every setting).
  * key 0: weight-pipeline shape of the fused bf16 kernel (0 = default; see mlp_bf16.hip launch_one).
  *        Values 50..58 once chose earlier generations of the weight-gradient launcher; they are still accepted and do nothing.
- * key 1: route of nerf_amd_density_value_grad (0 = default: the fused kernel where it covers the model, 1 = always two launches). */
+ * key 1: route of nerf_amd_density_value_grad (0 = default: the fused kernel where it covers the model, 1 = always two launches).
+ * key 2: where NERF_AMD_PREC_BF16 runs the folded stream (NERF_AMD_COPY_BF16_FOLD) of a view-branch model:
+ *        0 = default: in the no-grad render path (nerf_amd_render_batch and the render calls built on the same stages);
+ *            nerf_amd_nerf_forward stays unfolded and bit-equal to the training forward;
+ *        1 = nowhere (A/B leg: the unfolded kernels everywhere);
+ *        2 = in nerf_amd_nerf_forward too (tests, tools/mlp_ab.py). */
 int nerf_amd_set_tuning(int key, int value);
 int nerf_amd_profile_collect(int64_t launches[3], double total_ms[3], double total_points[3]);
 

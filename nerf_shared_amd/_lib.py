@@ -17,6 +17,7 @@ ABI_VERSION = 7
 PREC_FP32, PREC_BF16, PREC_FP32_SPLIT = 0, 1, 2
 # packed copies of a model's parameters (include/nerf_amd.h NERF_AMD_COPY_*) and which of them a call needs
 COPY_BF16, COPY_BWD, COPY_SPLIT, COPY_BWD_SPLIT, COPY_FP32, COPY_FP32_BWD, COPY_ALL = 1, 2, 4, 8, 16, 32, 63
+COPY_BF16_FOLD = 128         # the folded bf16 stream of a view-branch model (not in COPY_ALL: packed only for the calls that render)
 COPY_OF = {PREC_BF16: COPY_BF16, PREC_FP32_SPLIT: COPY_SPLIT, PREC_FP32: COPY_FP32}                    # inference
 TRAIN_COPIES = {PREC_BF16: COPY_BF16 | COPY_BWD, PREC_FP32_SPLIT: COPY_SPLIT | COPY_BWD_SPLIT,       # forward_train + backward
                 PREC_FP32: COPY_FP32 | COPY_FP32_BWD}

@@ -66,6 +66,9 @@ namespace na {
 // tuning knob (nerf_amd_set_tuning key 0): 0 = 16x16x32 kernel, 100+ = the shapes of mlp_bf16.hip (launch_one).  Atomic: the
 // launchers of concurrent host threads read it while nerf_amd_set_tuning may write it (nerf_amd.h threading contract).
 std::atomic<int> g_variant{0};
+// nerf_amd_set_tuning key 2: where bf16 view-branch models run the folded stream (feature_linear folded into views_linears.0):
+// 0 the no-grad render path, 1 nowhere, 2 nerf_amd_nerf_forward too
+std::atomic<int> g_fold{0};
 
 int tile_counters_init(int device) {
     if (device < 0 || device >= 16) return NERF_AMD_EINVAL;
@@ -106,6 +109,11 @@ struct nerf_amd_model {
     TileDesc *d_tiles16 = nullptr;
     TrainLayerF32 *d_tlayers = nullptr;  // train_f32.hip: per-layer descriptors and the transposed fp32 stream
     float *stream_f32_t = nullptr;
+    // the folded s16 stream (program.h frags16_fold), its bias table and the fp32 FOLD tensor it is packed from
+    FragDesc *d_frags16_fold = nullptr;
+    TileDesc *d_tiles16_fold = nullptr;
+    uint16_t *stream_s16_fold = nullptr;
+    float *bias_s16_fold = nullptr, *fold_w = nullptr, *fold_b = nullptr;
     int fresh = 0;                       // NERF_AMD_COPY_* of the packed copies that hold the current parameters
 };
 
@@ -131,11 +139,14 @@ int nerf_amd_model_create(const nerf_amd_arch *arch, int device, nerf_amd_model 
     }
     const Program &p = m->prog;
     int rc;
+    std::vector<TensorDesc> tensors_dev(p.tensors);      // + the FOLD tensor at p.fold_tensor (the pack kernels' table only)
+    if (p.fold_tensor >= 0) tensors_dev.push_back({p.arch.W / 2, p.arch.W + p.input_ch_views});
     if ((rc = upload(&m->d_frags, p.frags)) || (rc = upload(&m->d_tiles, p.tiles)) ||
         (rc = upload(&m->d_frags16, p.frags16)) || (rc = upload(&m->d_tiles16, p.tiles16)) ||
         (rc = upload(&m->d_frags_bwd, p.frags_bwd)) || (rc = upload(&m->d_frags_split, p.frags_split)) ||
         (rc = upload(&m->d_frags_bwd_split, p.frags_bwd_split)) ||
-        (rc = upload(&m->d_layers, p.layers)) || (rc = upload(&m->d_tensors, p.tensors)) || (rc = upload(&m->d_tlayers, p.tlayers))) {
+        (rc = upload(&m->d_frags16_fold, p.frags16_fold)) || (rc = upload(&m->d_tiles16_fold, p.tiles16_fold)) ||
+        (rc = upload(&m->d_layers, p.layers)) || (rc = upload(&m->d_tensors, tensors_dev)) || (rc = upload(&m->d_tlayers, p.tlayers))) {
         nerf_amd_model_destroy(m);
         return rc;
     }
@@ -148,6 +159,13 @@ int nerf_amd_model_create(const nerf_amd_arch *arch, int device, nerf_amd_model 
         if (e == hipSuccess && !p.frags_bwd.empty())
             e = hipMalloc(reinterpret_cast<void **>(&m->stream_bwd), p.frags_bwd.size() * 1024);
         if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&m->stream_split), p.frags_split.size() * 1024);
+        if (e == hipSuccess && !p.frags16_fold.empty()) {
+            const size_t rows = (size_t)p.arch.W / 2, cols = (size_t)p.arch.W + p.input_ch_views;
+            e = hipMalloc(reinterpret_cast<void **>(&m->stream_s16_fold), p.frags16_fold.size() * 1024);
+            if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&m->bias_s16_fold), p.tiles16_fold.size() * 16 * sizeof(float));
+            if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&m->fold_w), rows * cols * sizeof(float));
+            if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&m->fold_b), rows * sizeof(float));
+        }
         if (e == hipSuccess && !p.frags_bwd_split.empty())
             e = hipMalloc(reinterpret_cast<void **>(&m->stream_bwd_split), p.frags_bwd_split.size() * 1024);
     }
@@ -167,7 +185,7 @@ int nerf_amd_model_create(const nerf_amd_arch *arch, int device, nerf_amd_model 
 int nerf_amd_model_update_copies(nerf_amd_model *m, const float *const *weights, const float *const *biases,
                                  int n_tensors, int copies, int others_current, void *stream) {
     if (!m || !weights || !biases) return fail(NERF_AMD_EINVAL, "null argument");
-    if (copies & ~NERF_AMD_COPY_ALL) return fail(NERF_AMD_EINVAL, "unknown copy bits");
+    if (copies & ~(NERF_AMD_COPY_ALL | NERF_AMD_COPY_BF16_FOLD)) return fail(NERF_AMD_EINVAL, "unknown copy bits");
     const Program &p = m->prog;
     if (n_tensors != (int)p.tensors.size())
         return fail(NERF_AMD_EINVAL, "expected " + std::to_string(p.tensors.size()) + " parameter tensors, got " + std::to_string(n_tensors));
@@ -184,6 +202,10 @@ int nerf_amd_model_update_copies(nerf_amd_model *m, const float *const *weights,
                          m->d_frags16, m->d_tiles16, m->stream_s16, m->bias_s16, m->d_frags_bwd, m->stream_bwd,
                          m->d_frags_split, m->stream_split, m->d_frags_bwd_split, m->stream_bwd_split, m->d_tlayers, m->stream_f32_t,
                          copies, s);
+    // the folded stream: launches of its own, only when asked for (a captured training step packs what it always packed)
+    if (!rc && (copies & NERF_AMD_COPY_BF16_FOLD) && m->stream_s16_fold)
+        rc = launch_pack_fold(p, m->d_frags16_fold, m->d_tiles16_fold, m->d_tensors, wt, bt, m->fold_w, m->fold_b, m->stream_s16_fold,
+                              m->bias_s16_fold, s);
     if (rc) return fail(rc, "pack launch failed");
     m->fresh = (others_current ? m->fresh : 0) | copies;
     return NERF_AMD_OK;
@@ -202,6 +224,8 @@ void nerf_amd_model_destroy(nerf_amd_model *m) {
     (void)hipFree(m->d_frags16); (void)hipFree(m->d_tiles16); (void)hipFree(m->stream_s16); (void)hipFree(m->bias_s16);
     (void)hipFree(m->stream_bf16); (void)hipFree(m->bias_bf16); (void)hipFree(m->stream_f32); (void)hipFree(m->bias_f32);
     (void)hipFree(m->d_tlayers); (void)hipFree(m->stream_f32_t);
+    (void)hipFree(m->d_frags16_fold); (void)hipFree(m->d_tiles16_fold); (void)hipFree(m->stream_s16_fold);
+    (void)hipFree(m->bias_s16_fold); (void)hipFree(m->fold_w); (void)hipFree(m->fold_b);
     delete m;
 }
 
@@ -219,15 +243,16 @@ int nerf_amd_model_out_ch(const nerf_amd_model *m) { return m ? m->prog.out_ch :
 
 int nerf_amd_pack_bf16_host(const nerf_amd_arch *arch, int shape, const float *const *weights, const float *const *biases,
                             int n_tensors, uint16_t *stream_out, int64_t *n_frags, float *bias_out, int64_t *n_bias) {
-    if (shape != 16 && shape != 32 && shape != 17 && shape != 18 && shape != 19)
-        return fail(NERF_AMD_EINVAL, "shape must be 32 (32x32x16 stream), 16 (16x16x32 stream), 17 (backward stream), 18 (split-precision stream) or 19 (split-precision backward stream)");
+    if (shape != 16 && shape != 32 && shape != 17 && shape != 18 && shape != 19 && shape != 20)
+        return fail(NERF_AMD_EINVAL, "shape must be 32 (32x32x16 stream), 16 (16x16x32 stream), 17 (backward stream), 18 (split-precision stream), 19 (split-precision backward stream) or 20 (folded 16x16x32 stream)");
     if (!arch) return fail(NERF_AMD_EINVAL, "null argument");
     Program p;
     const char *err = "";
     if (build_program(*arch, p, &err) != 0) return fail(NERF_AMD_EINVAL, err);
     if (!p.bf16_ok) return fail(NERF_AMD_EUNSUPPORTED, "architecture has no fused bf16 program (needs D=8, W=256, skips=[4])");
-    if (n_frags) *n_frags = (int64_t)(shape == 19 ? p.frags_bwd_split.size() : shape == 18 ? p.frags_split.size() : shape == 17 ? p.frags_bwd.size() : shape == 16 ? p.frags16.size() : p.frags.size());
-    if (n_bias) *n_bias = (shape == 17 || shape == 18 || shape == 19) ? 0 : shape == 16 ? (int64_t)p.tiles16.size() * 16 : (int64_t)p.tiles.size() * 32;
+    if (shape == 20 && p.fold_tensor < 0) return fail(NERF_AMD_EUNSUPPORTED, "architecture has no view branch: nothing to fold");
+    if (n_frags) *n_frags = (int64_t)(shape == 20 ? p.frags16_fold.size() : shape == 19 ? p.frags_bwd_split.size() : shape == 18 ? p.frags_split.size() : shape == 17 ? p.frags_bwd.size() : shape == 16 ? p.frags16.size() : p.frags.size());
+    if (n_bias) *n_bias = (shape == 17 || shape == 18 || shape == 19) ? 0 : shape == 20 ? (int64_t)p.tiles16_fold.size() * 16 : shape == 16 ? (int64_t)p.tiles16.size() * 16 : (int64_t)p.tiles.size() * 32;
     if (stream_out || bias_out) {
         if (!weights || !biases || n_tensors != (int)p.tensors.size()) return fail(NERF_AMD_EINVAL, "bad parameter list");
         pack_bf16_host(p, shape, weights, biases, stream_out, bias_out);
@@ -273,9 +298,20 @@ void set_model_constants(MlpArgs &a, const nerf_amd_model *m) {
     a.out_ch = p.out_ch;
 }
 
-int run_field(const nerf_amd_model *m, MlpArgs a, int precision, hipStream_t s) {
+// fold_mode: what tuning key 2 lets this caller do with the folded stream of a bf16 view-branch model of the fused family
+// (16x16x32 kernels).  FOLD_IF_CURRENT (the render path): taken when the folded copy holds the current parameters
+// (NERF_AMD_COPY_BF16_FOLD: asked for by whoever renders), else the unfolded stream as always.  FOLD_REQUIRED (key 2 = 2,
+// nerf_amd_nerf_forward): a missing copy is an error, so a test of the folded kernel cannot pass on the unfolded one.
+enum { FOLD_NEVER = 0, FOLD_IF_CURRENT = 1, FOLD_REQUIRED = 2 };
+int run_field(const nerf_amd_model *m, MlpArgs a, int precision, hipStream_t s, int fold_mode = FOLD_NEVER) {
     const Program &p = m->prog;
     if (int rc0 = need_copy(m, copy_for(precision))) return rc0;
+    const int variant = g_variant.load(std::memory_order_relaxed);
+    const bool foldable = precision == NERF_AMD_PREC_BF16 && m->stream_s16_fold && nerf_amd_model_supports_bf16(m) &&
+                          variant < 100 && variant != 40;      // (40: the round-1 shape of the A/B table has no folded twin)
+    if (fold_mode == FOLD_REQUIRED && foldable)
+        if (int rc0 = need_copy(m, NERF_AMD_COPY_BF16_FOLD)) return rc0;
+    const bool fold = fold_mode != FOLD_NEVER && foldable && (m->fresh & NERF_AMD_COPY_BF16_FOLD);
     a.stream_bf16 = m->stream_bf16; a.bias_bf16 = m->bias_bf16;
     a.stream_s16 = m->stream_s16; a.bias_s16 = m->bias_s16;
     a.stream_split = m->stream_split;
@@ -314,6 +350,10 @@ int run_field(const nerf_amd_model *m, MlpArgs a, int precision, hipStream_t s) 
         if (g_variant >= 100)   // A/B: the first-generation 32x32x16 kernel
             rc = launch_mlp_bf16(a, p.arch.multires, p.arch.multires_views, p.arch.use_viewdirs, p.n_frags_used, (int)p.tiles.size(), s);
         else {
+            if (fold) {
+                a.stream_s16 = m->stream_s16_fold; a.bias_s16 = m->bias_s16_fold;
+                rc = launch_mlp_bf16_s16(a, p.arch.multires, p.arch.multires_views, 1, p.n_frags16_fold_used, (int)p.tiles16_fold.size(), s, true);
+            } else
             rc = launch_mlp_bf16_s16(a, p.arch.multires, p.arch.multires_views, p.arch.use_viewdirs, p.n_frags16_used, (int)p.tiles16.size(), s);
             if (rc == NERF_AMD_EUNSUPPORTED)   // e.g. output_ch > 16: the 32x32x16 kernel covers it
                 rc = launch_mlp_bf16(a, p.arch.multires, p.arch.multires_views, p.arch.use_viewdirs, p.n_frags_used, (int)p.tiles.size(), s);
@@ -342,7 +382,8 @@ int nerf_amd_nerf_forward(const nerf_amd_model *m, const float *pts, const float
     MlpArgs a{};
     set_inputs(a, pts, viewdirs, nullptr, 0, nullptr, true);      // (run_field drops viewdirs for a model without view branch)
     a.P = n_rays * n_samples; a.S = n_samples; a.out = out;
-    return run_field(m, a, precision, static_cast<hipStream_t>(stream));
+    return run_field(m, a, precision, static_cast<hipStream_t>(stream),
+                     g_fold.load(std::memory_order_relaxed) == 2 ? FOLD_REQUIRED : FOLD_NEVER);
 }
 
 int nerf_amd_mlp_embedded(const nerf_amd_model *m, const float *x, int64_t n, float *out, void *stream) {
@@ -780,14 +821,15 @@ int stage_z(ChunkPlan &p, hipStream_t s) {
 }
 
 int stage_field(const ChunkPlan &p, bool fine_pass, hipStream_t s) {
+    const int fold_wanted = g_fold.load(std::memory_order_relaxed) != 1 ? FOLD_IF_CURRENT : FOLD_NEVER;      // the no-grad render path
     MlpArgs a{};
     set_inputs(a, nullptr, nullptr, p.io->rays, p.io->ray_ch, fine_pass ? p.z_f : p.z_c, p.has_vd);
     if (!fine_pass) {
         a.P = p.R * p.Nc; a.S = p.Nc; a.out = p.raw_c;
-        return run_field(p.coarse, a, p.cfg->precision, s);
+        return run_field(p.coarse, a, p.cfg->precision, s, fold_wanted);
     }
     a.P = p.R * (int64_t)p.Nf; a.S = p.Nf; a.out = p.raw_f;
-    return run_field(p.fm, a, p.cfg->precision, s);
+    return run_field(p.fm, a, p.cfg->precision, s, fold_wanted);
 }
 
 CompositeJob final_job(const ChunkPlan &p) {       // compositing of the last pass of a chunk
@@ -1071,6 +1113,7 @@ extern "C" {
 int nerf_amd_set_tuning(int key, int value) {
     if (key == 0 && value >= 0 && value <= 115) { g_variant.store(value, std::memory_order_relaxed); return NERF_AMD_OK; }
     if (key == 1 && value >= 0 && value <= 1) { g_density_route.store(value, std::memory_order_relaxed); return NERF_AMD_OK; }
+    if (key == 2 && value >= 0 && value <= 2) { g_fold.store(value, std::memory_order_relaxed); return NERF_AMD_OK; }
     return fail(NERF_AMD_EINVAL, "unknown tuning key/value");
 }
 

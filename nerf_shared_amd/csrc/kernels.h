@@ -101,9 +101,14 @@ int launch_pack(const Program &p, const FragDesc *d_frags, const TileDesc *d_til
                 const FragDesc *d_frags16, const TileDesc *d_tiles16, uint16_t *stream_s16, float *bias_s16,
                 const FragDesc *d_frags_bwd, uint16_t *stream_bwd, const FragDesc *d_frags_split, uint16_t *stream_split,
                 const FragDesc *d_frags_bwd_split, uint16_t *stream_bwd_split, const TrainLayerF32 *d_tlayers, float *stream_f32_t, int copies, hipStream_t s);
+// the folded s16 stream (program.h frags16_fold): fold_kernel into the model's scratch tensor, then its fragments and bias
+// tiles; d_tensors has the FOLD tensor's entry at p.fold_tensor.  A no-op for a model with nothing to fold.
+int launch_pack_fold(const Program &p, const FragDesc *d_frags16_fold, const TileDesc *d_tiles16_fold, const TensorDesc *d_tensors,
+                     PtrTable d_weight_ptrs, PtrTable d_bias_ptrs, float *fold_w, float *fold_b, uint16_t *stream_s16_fold,
+                     float *bias_s16_fold, hipStream_t s);
 void pack_bf16_host(const Program &p, int shape, const float *const *w, const float *const *b, uint16_t *stream, float *bias);
 int launch_mlp_bf16_s16(const MlpArgs &a, int multires, int multires_views, int use_viewdirs,
-                        int n_frags_used, int n_tiles, hipStream_t s);
+                        int n_frags_used, int n_tiles, hipStream_t s, bool fold = false);
 // training kernels: the view-branch model with multires 10/4 or 15/6, the output_linear model with multires 10 or 15
 int launch_mlp_bf16_s16_save(const MlpArgs &a, int multires, int multires_views, int use_viewdirs, int n_frags_used, int n_tiles, hipStream_t s);
 int launch_mlp_bwd_s16(const MlpArgs &a, int multires, int multires_views, int use_viewdirs, int n_frags_used, hipStream_t s);

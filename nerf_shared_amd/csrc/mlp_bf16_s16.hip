@@ -272,8 +272,11 @@ __device__ __forceinline__ void save_bits(uint8_t *base, const bf16x8 *y, const 
     });
 }
 
-template <int LX, int LD, bool VD>
+// FOLD (view-branch models, inference): the stream without the feature layer (program.h frags16_fold) -- views_linears.0
+// reads h8 through W' = Wv[:, :W] . Wf, so the layer-7 output registers feed the views layer directly.
+template <int LX, int LD, bool VD, bool FOLD = false>
 struct Layout16 {
+    static_assert(VD || !FOLD, "only a view branch has a feature layer to fold");
     static constexpr int KE = gen16_ksteps(LX);
     static constexpr int KD = VD ? gen16_ksteps(LD) : 0;
     static constexpr int F_L0 = 0;
@@ -282,17 +285,19 @@ struct Layout16 {
     static constexpr int F_L6 = F_L5 + 16 * (KE + 8);
     static constexpr int F_HEAD = F_L6 + 2 * 128;
     static constexpr int F_FEAT = F_HEAD;
-    static constexpr int F_ALPHA = F_FEAT + 128;
+    static constexpr int F_ALPHA = F_FEAT + (FOLD ? 0 : 128);
     static constexpr int F_VIEWS = F_ALPHA + 8;
     static constexpr int F_RGB = F_VIEWS + 8 * (8 + KD);
     static constexpr int F_END = VD ? F_RGB + 4 : F_HEAD + 8;
-    static constexpr int N_TILES = VD ? 128 + 16 + 1 + 8 + 1 : 128 + 1;
+    static constexpr int T_ALPHA = 128 + (FOLD ? 0 : 16), T_VIEWS = T_ALPHA + 1, T_RGB = T_VIEWS + 8;      // bias tiles of the heads
+    static constexpr int N_TILES = VD ? T_RGB + 1 : 128 + 1;
 };
 
-template <int LX, int LD, bool VD, class C, bool SAVE = false>
-__global__ __launch_bounds__(C::WAVES * 64, 2) void mlp_bf16_s16_kernel(MlpArgs a) {
+template <int LX, int LD, bool VD, class C, bool SAVE, bool FOLD>
+__device__ __forceinline__ void mlp_bf16_s16_body(const MlpArgs &a) {
+    static_assert(!(SAVE && FOLD), "the training forward saves feat: it keeps the unfolded stream");
     constexpr int WG_THREADS = C::WAVES * 64, WG_POINTS = C::WAVES * 32;
-    using Lay = Layout16<LX, LD, VD>;
+    using Lay = Layout16<LX, LD, VD, FOLD>;
     constexpr int KE = Lay::KE, KD = Lay::KD, NF = Lay::F_END, NB = (NF + C::BF - 1) / C::BF;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     float *bias_lds = reinterpret_cast<float *>(smem + C::RING_BYTES);
@@ -439,13 +444,19 @@ __global__ __launch_bounds__(C::WAVES * 64, 2) void mlp_bf16_s16_kernel(MlpArgs 
     if constexpr (SAVE) { save_frags<8, 256>(a.sv_h + 7 * HS, B, pidx, q); save_bits<8>(a.sv_bits + 7 * BS, B, pidx, q); }
 
     if constexpr (VD) {
+        f32x4 alpha[2], rgb[2];
+        if constexpr (FOLD) {
+            tile_single<Lay::F_ALPHA, Lay::T_ALPHA, 8, NB, NF>(c, B, alpha);               // row 0 = sigma
+            layer16<Lay::F_VIEWS, Lay::T_VIEWS, 4, 8, KD, true, NB, NF>(c, B, Dv, A);      // views_linears.0 over [W' | dirs]: reads h8
+            tile_single<Lay::F_RGB, Lay::T_RGB, 4, NB, NF>(c, A, rgb);                     // rows 0..2
+        } else {
         layer16<Lay::F_FEAT, 128, 8, 8, 0, false, NB, NF>(c, B, B, A);     // feature (no activation)
         if constexpr (SAVE) save_frags<8, 256>(a.sv_feat, A, pidx, q);
-        f32x4 alpha[2], rgb[2];
-        tile_single<Lay::F_ALPHA, 144, 8, NB, NF>(c, B, alpha);            // row 0 = sigma
-        layer16<Lay::F_VIEWS, 145, 4, 8, KD, true, NB, NF>(c, A, Dv, B);   // views_linears.0 (128 rows)
+        tile_single<Lay::F_ALPHA, Lay::T_ALPHA, 8, NB, NF>(c, B, alpha);   // row 0 = sigma
+        layer16<Lay::F_VIEWS, Lay::T_VIEWS, 4, 8, KD, true, NB, NF>(c, A, Dv, B);   // views_linears.0 (128 rows)
         if constexpr (SAVE) { save_frags<4, 128>(a.sv_hv, B, pidx, q); save_bits<4>(a.sv_bits + 8 * BS, B, pidx, q); }
-        tile_single<Lay::F_RGB, 153, 4, NB, NF>(c, B, rgb);                // rows 0..2
+        tile_single<Lay::F_RGB, Lay::T_RGB, 4, NB, NF>(c, B, rgb);         // rows 0..2
+        }
         static_for<2>([&](auto cc_) {
             constexpr int cc = cc_;
             if (valid[cc] && q == 0) {
@@ -485,6 +496,16 @@ __global__ __launch_bounds__(C::WAVES * 64, 2) void mlp_bf16_s16_kernel(MlpArgs 
     }
 }
 
+template <int LX, int LD, bool VD, class C, bool SAVE = false>
+__global__ __launch_bounds__(C::WAVES * 64, 2) void mlp_bf16_s16_kernel(MlpArgs a) {
+    mlp_bf16_s16_body<LX, LD, VD, C, SAVE, false>(a);
+}
+// (a kernel name of its own, not one more template argument: the ISA checks and the profiles select kernels by name)
+template <int LX, int LD, class C>
+__global__ __launch_bounds__(C::WAVES * 64, 2) void mlp_bf16_s16_kernel_fold(MlpArgs a) {
+    mlp_bf16_s16_body<LX, LD, true, C, false, true>(a);
+}
+
 
 // ---------------------------------------------------------------------------------------------------------
 // The pipelined form of the kernel above (inference; the training forward keeps the simple one).  Same
@@ -498,11 +519,11 @@ __global__ __launch_bounds__(C::WAVES * 64, 2) void mlp_bf16_s16_kernel(MlpArgs 
 //     of layers 6 and 7 (the xyz encoding is dead after the skip layer, so it is overwritten in place; the
 //     view-direction encoding is double-buffered), i.e. in the VALU slots the MFMAs leave free.
 // ---------------------------------------------------------------------------------------------------------
-template <int LX, int LD, bool VD, class C>
-__global__ __launch_bounds__(C::WAVES * 64, 2) void mlp_bf16_s16p_kernel(MlpArgs a) {
+template <int LX, int LD, bool VD, class C, bool FOLD>
+__device__ __forceinline__ void mlp_bf16_s16p_body(const MlpArgs &a) {
     static_assert((C::OPT & 32) != 0 && C::PHASE > 0, "the pipelined kernel needs the continuous ring");
     constexpr int WG_THREADS = C::WAVES * 64, WG_POINTS = C::WAVES * 32;
-    using Lay = Layout16<LX, LD, VD>;
+    using Lay = Layout16<LX, LD, VD, FOLD>;
     constexpr int KE = Lay::KE, KD = Lay::KD, NF = Lay::F_END, NB = (NF + C::BF - 1) / C::BF;
     constexpr int SHIFT = NB % C::NS;                      // ring slots the block numbering advances per tile
     using EncX = Enc16<LX, KE>;
@@ -516,11 +537,16 @@ __global__ __launch_bounds__(C::WAVES * 64, 2) void mlp_bf16_s16p_kernel(MlpArgs
     //     so only one point's raw coordinates and encoder state are live at a time (registers are what limits this);
     //   feature layer (16 slots, view-branch models): THIS tile's view directions -- loads, then 2 x NSD steps -- which
     //     nothing needs before the views layer that follows.
+    //   FOLD: there is no feature layer, and layers 6 + 7 are full.  The view directions hang on the skip layer (layer 5)
+    //     instead: its 8 pairs x (KE + 8) k-steps start on a block boundary, so counting k-steps g through the layer its
+    //     syncs sit in front of g = 4 (mod 8), and slot g / 4 (g = 0 mod 4) keeps the rule above -- odd slots right behind a
+    //     sync, even ones half a block later.  Dv (8 x KD VGPRs) then stays live over layers 6 + 7.
     constexpr int NSX = EncX::NSTEP, NSD = VD ? EncD::NSTEP : 0;
     constexpr int PT_SLOTS = 4 + NSX + ((4 + NSX) & 1);           // load (odd slot), two slots later the point, then the steps; even length
     constexpr int SLOT_LOAD = 1, SLOT_PTS = 3, SLOT_ENC = 4;       // relative to a point's first slot
     static_assert(C::BF == 16 && C::PHASE == 8, "hook slots are laid out for a sync in front of k-step 4");
     static_assert(2 * PT_SLOTS <= 32 && 3 + 2 * NSD <= 16, "the encodings must fit on the hooks they are given");
+    static_assert(Lay::F_L5 % C::BF == 0 && 3 + 2 * NSD <= 2 * (KE + 8), "the skip layer's slots (FOLD)");
     extern __shared__ __attribute__((aligned(16))) char smem[];
     float *bias_lds = reinterpret_cast<float *>(smem + C::RING_BYTES);
     lds_u32_t *ticket_lds = (lds_u32_t *)(uintptr_t)(uint32_t)(uintptr_t)(bias_lds + Lay::N_TILES * 16);     // the tile after next (dynamic deal)
@@ -674,10 +700,9 @@ __global__ __launch_bounds__(C::WAVES * 64, 2) void mlp_bf16_s16p_kernel(MlpArgs
             }
         }
     };
-    auto hook_feat = [&](auto p_, auto k_) {
-        constexpr int p = p_, k = k_;
-        if constexpr (VD && (k == 0 || k == 4)) {
-            constexpr int slot = 2 * p + (k == 4);
+    auto dirs_slot = [&](auto slot_) {       // this tile's view directions: slot 1 the loads, slots 3 .. the encoding steps
+        constexpr int slot = slot_;
+        if constexpr (VD) {
             if constexpr (slot == 1) issue_dir_loads();
             if constexpr (slot >= 3 && slot < 3 + 2 * NSD) {
                 constexpr int cc = (slot - 3) / NSD, st = (slot - 3) % NSD;
@@ -686,6 +711,14 @@ __global__ __launch_bounds__(C::WAVES * 64, 2) void mlp_bf16_s16p_kernel(MlpArgs
                 if constexpr (st == NSD - 1) ed.template finish<2>(q >> 1, q & 1, Dv + cc);
             }
         }
+    };
+    auto hook_feat = [&](auto p_, auto k_) {
+        constexpr int p = p_, k = k_;
+        if constexpr (k == 0 || k == 4) dirs_slot(std::integral_constant<int, 2 * p + (k == 4)>{});
+    };
+    auto hook5 = [&](auto p_, auto k_) {     // FOLD: k-step g of the skip layer
+        constexpr int g = p_ * (KE + 8) + k_;
+        if constexpr (FOLD && g % 4 == 0) dirs_slot(std::integral_constant<int, g / 4>{});
     };
     auto hook6 = [&](auto p_, auto k_) {
         constexpr int p = p_, k = k_;
@@ -724,16 +757,23 @@ __global__ __launch_bounds__(C::WAVES * 64, 2) void mlp_bf16_s16p_kernel(MlpArgs
     layer16<Lay::F_L1 + 1 * 128, 32, 8, 8, 0, true, NB, NF>(c, B, B, A);
     layer16<Lay::F_L1 + 2 * 128, 48, 8, 8, 0, true, NB, NF>(c, A, A, B);
     layer16<Lay::F_L1 + 3 * 128, 64, 8, 8, 0, true, NB, NF>(c, B, B, A);
-    layer16<Lay::F_L5, 80, 8, KE, 8, true, NB, NF>(c, E, A, B);            // skip: [input_pts | h]
+    if constexpr (FOLD) layer16<Lay::F_L5, 80, 8, KE, 8, true, NB, NF>(c, E, A, B, hook5);     // skip + this tile's view directions
+    else layer16<Lay::F_L5, 80, 8, KE, 8, true, NB, NF>(c, E, A, B);       // skip: [input_pts | h]
     layer16<Lay::F_L6, 96, 8, 8, 0, true, NB, NF>(c, B, B, A, hook6);      // + next tile: loads, points, encoding ...
     layer16<Lay::F_L6 + 128, 112, 8, 8, 0, true, NB, NF>(c, A, A, B, hook7);   // ... h7 in B
 
     if constexpr (VD) {
-        layer16<Lay::F_FEAT, 128, 8, 8, 0, false, NB, NF>(c, B, B, A, hook_feat);   // feature (no activation) + this tile's view directions
         f32x4 alpha[2], rgb[2];
-        tile_single<Lay::F_ALPHA, 144, 8, NB, NF>(c, B, alpha);            // row 0 = sigma
-        layer16<Lay::F_VIEWS, 145, 4, 8, KD, true, NB, NF>(c, A, Dv, B);   // views_linears.0 (128 rows)
-        tile_single<Lay::F_RGB, 153, 4, NB, NF>(c, B, rgb);                // rows 0..2
+        if constexpr (FOLD) {
+            tile_single<Lay::F_ALPHA, Lay::T_ALPHA, 8, NB, NF>(c, B, alpha);               // row 0 = sigma
+            layer16<Lay::F_VIEWS, Lay::T_VIEWS, 4, 8, KD, true, NB, NF>(c, B, Dv, A);      // views_linears.0 over [W' | dirs]: reads h8
+            tile_single<Lay::F_RGB, Lay::T_RGB, 4, NB, NF>(c, A, rgb);                     // rows 0..2
+        } else {
+        layer16<Lay::F_FEAT, 128, 8, 8, 0, false, NB, NF>(c, B, B, A, hook_feat);   // feature (no activation) + this tile's view directions
+        tile_single<Lay::F_ALPHA, Lay::T_ALPHA, 8, NB, NF>(c, B, alpha);   // row 0 = sigma
+        layer16<Lay::F_VIEWS, Lay::T_VIEWS, 4, 8, KD, true, NB, NF>(c, A, Dv, B);   // views_linears.0 (128 rows)
+        tile_single<Lay::F_RGB, Lay::T_RGB, 4, NB, NF>(c, B, rgb);         // rows 0..2
+        }
         static_for<2>([&](auto cc_) {
             constexpr int cc = cc_;
             const int32_t p = point_index(tile, cc);
@@ -783,6 +823,15 @@ __global__ __launch_bounds__(C::WAVES * 64, 2) void mlp_bf16_s16p_kernel(MlpArgs
     }
 }
 
+template <int LX, int LD, bool VD, class C>
+__global__ __launch_bounds__(C::WAVES * 64, 2) void mlp_bf16_s16p_kernel(MlpArgs a) {
+    mlp_bf16_s16p_body<LX, LD, VD, C, false>(a);
+}
+template <int LX, int LD, class C>
+__global__ __launch_bounds__(C::WAVES * 64, 2) void mlp_bf16_s16p_kernel_fold(MlpArgs a) {
+    mlp_bf16_s16p_body<LX, LD, true, C, true>(a);
+}
+
 // density_grad.hip includes this file for the device templates above (NA_DEVICE_TEMPLATES_ONLY): the launchers below
 // belong to this translation unit alone.
 #ifndef NA_DEVICE_TEMPLATES_ONLY
@@ -792,29 +841,33 @@ static MlpArgs stamped(MlpArgs a) { a.stamps = g_stamp_buf; return a; }
 static const MlpArgs &stamped(const MlpArgs &a) { return a; }
 #endif
 
-template <int LX, int LD, bool VD, class C>
+template <int LX, int LD, bool VD, class C, bool FOLD = false>
 static int launch_wg16p(const MlpArgs &a, int n_frags_used, int n_tiles, hipStream_t s) {
     constexpr int WG_THREADS = C::WAVES * 64, WG_POINTS = C::WAVES * 32;
-    using Lay = Layout16<LX, LD, VD>;
+    using Lay = Layout16<LX, LD, VD, FOLD>;
     if (n_frags_used != Lay::F_END || n_tiles != Lay::N_TILES) return NERF_AMD_EINVAL;
     const size_t lds = C::RING_BYTES + (size_t)Lay::N_TILES * 16 * sizeof(float) + 16;      // + the ticket word
     static DynamicLdsOptIn opt_in;
     // one workgroup per CU walks the tiles
-    return launch_field({reinterpret_cast<const void *>(mlp_bf16_s16p_kernel<LX, LD, VD, C>), &opt_in, lds, WG_THREADS, WG_POINTS, 1},
-                        stamped(a), s);
+    const void *kernel;
+    if constexpr (FOLD) kernel = reinterpret_cast<const void *>(mlp_bf16_s16p_kernel_fold<LX, LD, C>);
+    else kernel = reinterpret_cast<const void *>(mlp_bf16_s16p_kernel<LX, LD, VD, C>);
+    return launch_field({kernel, &opt_in, lds, WG_THREADS, WG_POINTS, 1}, stamped(a), s);
 }
 
-template <int LX, int LD, bool VD, class C, bool SAVE = false>
+template <int LX, int LD, bool VD, class C, bool SAVE = false, bool FOLD = false>
 static int launch_wg16(const MlpArgs &a, int n_frags_used, int n_tiles, hipStream_t s) {
     constexpr int WG_THREADS = C::WAVES * 64, WG_POINTS = C::WAVES * 32;
-    using Lay = Layout16<LX, LD, VD>;
+    using Lay = Layout16<LX, LD, VD, FOLD>;
     if (n_frags_used != Lay::F_END || n_tiles != Lay::N_TILES) return NERF_AMD_EINVAL;
     const size_t lds = C::RING_BYTES + (size_t)Lay::N_TILES * 16 * sizeof(float) + 16;      // + the ticket word
     static DynamicLdsOptIn opt_in;         // per kernel instantiation, tracks every device (launch_util.h)
     // one workgroup per CU walks the tiles (+1 %: no per-tile dispatch; 4-wave workgroups: two per CU); 31 = A/B off
     const int wg_per_cu = g_variant != 31 ? 8 / C::WAVES : 0;
-    return launch_field({reinterpret_cast<const void *>(mlp_bf16_s16_kernel<LX, LD, VD, C, SAVE>), &opt_in, lds, WG_THREADS, WG_POINTS,
-                         wg_per_cu}, stamped(a), s);
+    const void *kernel;
+    if constexpr (FOLD) kernel = reinterpret_cast<const void *>(mlp_bf16_s16_kernel_fold<LX, LD, C>);
+    else kernel = reinterpret_cast<const void *>(mlp_bf16_s16_kernel<LX, LD, VD, C, SAVE>);
+    return launch_field({kernel, &opt_in, lds, WG_THREADS, WG_POINTS, wg_per_cu}, stamped(a), s);
 }
 
 // 64-KiB ring of 16-fragment blocks, mid-block sync, 4-deep read-ahead pinned in front of the MFMAs it runs ahead of
@@ -833,16 +886,24 @@ template <int LX, int LD> using CfgSaveT = Ctx<8, 16, 4, 8, 2>;   // the trainin
 #include "../../tools/experiments/field_variants_s16.inc"
 #endif
 
+// fold: a.stream_s16 / a.bias_s16 are the folded stream and its bias table (program.h frags16_fold; view-branch models)
 int launch_mlp_bf16_s16(const MlpArgs &a, int multires, int multires_views, int use_viewdirs,
-                        int n_frags_used, int n_tiles, hipStream_t s) {
+                        int n_frags_used, int n_tiles, hipStream_t s, bool fold) {
 #ifdef NERF_AMD_EXPERIMENTS      // A/B builds only: the variant table lives in tools/experiments/field_variants_s16.inc
-    {
+    if (!fold) {
         int rc_x = NERF_AMD_EUNSUPPORTED;
         if (experiment_launch_s16(a, multires, multires_views, use_viewdirs, n_frags_used, n_tiles, s, &rc_x)) return rc_x;
     }
 #endif
     return for_family(multires, multires_views, use_viewdirs, [&](auto f) -> int {
         if (!head_fits(f.vd, a.out_ch)) return NERF_AMD_EUNSUPPORTED;
+        if (fold) {
+            if constexpr (f.vd) {
+                if (g_variant == 41) return launch_wg16<f.lx, f.ld, true, Cfg16, false, true>(a, n_frags_used, n_tiles, s);
+                return launch_wg16p<f.lx, f.ld, true, Cfg16P, true>(a, n_frags_used, n_tiles, s);
+            }
+            return NERF_AMD_EINVAL;
+        }
         if constexpr (f.lx == 10 && f.ld == 4 && f.vd)
             if (g_variant == 40) return launch_wg16<10, 4, true, Cfg16R1>(a, n_frags_used, n_tiles, s);
         if (g_variant != 41) return launch_wg16p<f.lx, f.ld, f.vd, Cfg16P>(a, n_frags_used, n_tiles, s);

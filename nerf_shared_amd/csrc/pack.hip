@@ -187,6 +187,55 @@ __global__ __launch_bounds__(512) void pack_all_kernel(PackJobs J, PtrTable weig
         J.bias_f32[L.bias_off + i] = i < L.n_out ? biases[L.tensor][i] : 0.0f;
 }
 
+// The fold of feature_linear into views_linears.0 (program.h, frags16_fold): row o of the FOLD tensor,
+//   fold_w[o][i] = sum_k Wv[o][k] Wf[k][i] (i < W),  fold_w[o][W + j] = Wv[o][W + j],  fold_b[o] = sum_k Wv[o][k] bf[k] + bv[o],
+// from the fp32 parameters, k ascending in one fp32 fma chain: deterministic, and exact on small-integer weights.
+// 8.4 M MAC once per weight change; one block per row.  fold_row is shared with the host twin.
+NA_HD inline float fold_dot(const float *wv_row, const float *wf_col, int stride, int W) {
+    float acc = 0.0f;
+    for (int k = 0; k < W; ++k) acc = __builtin_fmaf(wv_row[k], wf_col[(int64_t)k * stride], acc);
+    return acc;
+}
+
+__global__ __launch_bounds__(256) void fold_kernel(const float *wf, const float *bf, const float *wv, const float *bv, int W, int n_views,
+                                                   float *fold_w, float *fold_b) {
+    const int o = blockIdx.x, n_in = W + n_views;
+    const float *row = wv + (int64_t)o * n_in;
+    for (int i = threadIdx.x; i < n_in; i += blockDim.x)
+        fold_w[(int64_t)o * n_in + i] = i < W ? fold_dot(row, wf + i, W, W) : row[i];
+    if (threadIdx.x == 0) fold_b[o] = fold_dot(row, bf, 1, W) + bv[o];
+}
+
+// The folded stream and its bias table: the tables' entry p.fold_tensor is the FOLD tensor.
+__global__ __launch_bounds__(512) void pack_fold_kernel(const FragDesc *frags, int n_frags, const TileDesc *tiles, int n_tiles,
+                                                        const TensorDesc *tensors, PtrTable weights_tab, PtrTable biases_tab,
+                                                        uint16_t *stream, float *bias) {
+    const int b = blockIdx.x;
+    if (b < n_frags) { pack_frag(frags, b, tensors, weights_tab.p, stream); return; }
+    const int e = (b - n_frags) * 512 + threadIdx.x;
+    if (e < n_tiles * 16) {
+        const TileDesc t = tiles[e >> 4];
+        const int row = t.row0 + (e & 15);
+        bias[e] = row < tensors[t.tensor].n_out ? biases_tab.p[t.tensor][row] : 0.0f;
+    }
+}
+
+int launch_pack_fold(const Program &p, const FragDesc *d_frags16_fold, const TileDesc *d_tiles16_fold, const TensorDesc *d_tensors,
+                     PtrTable d_w, PtrTable d_b, float *fold_w, float *fold_b, uint16_t *stream_s16_fold, float *bias_s16_fold,
+                     hipStream_t s) {
+    if (p.fold_tensor < 0 || p.frags16_fold.empty()) return NERF_AMD_OK;          // nothing to fold
+    if (p.fold_tensor >= MAX_TENSORS) return NERF_AMD_EINVAL;
+    const int D = p.arch.D, W = p.arch.W;
+    hipLaunchKernelGGL(fold_kernel, dim3(W / 2), dim3(256), 0, s, d_w.p[D], d_b.p[D], d_w.p[D + 2], d_b.p[D + 2], W,
+                       p.input_ch_views, fold_w, fold_b);
+    d_w.p[p.fold_tensor] = fold_w;
+    d_b.p[p.fold_tensor] = fold_b;
+    const int n_frags = (int)p.frags16_fold.size(), n_tiles = (int)p.tiles16_fold.size();
+    hipLaunchKernelGGL(pack_fold_kernel, dim3(n_frags + (n_tiles * 16 + 511) / 512), dim3(512), 0, s, d_frags16_fold, n_frags,
+                       d_tiles16_fold, n_tiles, d_tensors, d_w, d_b, stream_s16_fold, bias_s16_fold);
+    return hipGetLastError() == hipSuccess ? NERF_AMD_OK : NERF_AMD_EHIP;
+}
+
 int launch_pack(const Program &p, const FragDesc *d_frags, const TileDesc *d_tiles, const LayerF32 *d_layers,
                 const TensorDesc *d_tensors, const PtrTable &d_w, const PtrTable &d_b,
                 uint16_t *stream_bf16, float *bias_bf16, float *stream_f32, float *bias_f32,
@@ -223,6 +272,38 @@ int launch_pack(const Program &p, const FragDesc *d_frags, const TileDesc *d_til
 
 void pack_bf16_host(const Program &p, int shape, const float *const *w, const float *const *b,
                     uint16_t *stream, float *bias) {
+    if (shape == 20) {       // folded s16 stream and its bias table: the FOLD tensor first, like fold_kernel
+        if (p.fold_tensor < 0) return;
+        const int D = p.arch.D, W = p.arch.W, n_in = W + p.input_ch_views;
+        std::vector<float> fw((size_t)(W / 2) * n_in), fb(W / 2);
+        for (int o = 0; o < W / 2; ++o) {
+            const float *row = w[D + 2] + (int64_t)o * n_in;
+            for (int i = 0; i < n_in; ++i) fw[(size_t)o * n_in + i] = i < W ? fold_dot(row, w[D] + i, W, W) : row[i];
+            fb[o] = fold_dot(row, b[D], 1, W) + b[D + 2][o];
+        }
+        std::vector<const float *> ww(w, w + p.tensors.size()), bb(b, b + p.tensors.size());
+        ww.push_back(fw.data());
+        bb.push_back(fb.data());
+        std::vector<TensorDesc> td(p.tensors);
+        td.push_back({W / 2, n_in});
+        if (stream)
+            for (size_t n = 0; n < p.frags16_fold.size(); ++n)
+                for (int lane = 0; lane < 64; ++lane)
+                    for (int j = 0; j < 8; ++j) {
+                        int row;
+                        const FragDesc &d = p.frags16_fold[n];
+                        const TensorDesc &t = td[d.tensor];
+                        const int col = frag_source(d, lane, j, t.n_out, &row);
+                        stream[n * 512 + lane * 8 + j] = f32_to_bf16_rne(col < 0 ? 0.0f : ww[d.tensor][(int64_t)row * t.n_in + col]);
+                    }
+        if (bias)
+            for (size_t ti = 0; ti < p.tiles16_fold.size(); ++ti)
+                for (int r = 0; r < 16; ++r) {
+                    const TileDesc &t = p.tiles16_fold[ti];
+                    bias[ti * 16 + r] = t.row0 + r < td[t.tensor].n_out ? bb[t.tensor][t.row0 + r] : 0.0f;
+                }
+        return;
+    }
     if (shape == 17) {       // backward (transposed) stream; no bias table
         if (stream)
             for (size_t n = 0; n < p.frags_bwd.size(); ++n)

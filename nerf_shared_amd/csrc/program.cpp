@@ -179,6 +179,28 @@ int build_program(const nerf_amd_arch &a, Program &p, const char **err) {
         }
         p.n_frags16_used = (int)p.frags16.size();
         while (p.frags16.size() % STREAM_PAD_FRAGS) p.frags16.push_back({0, FRAG_ZERO, 0, 0, 0, 0, 0, 0});
+        // ---- folded s16 program: the same order without layer 8 (feature); the views layer reads the FOLD tensor
+        if (a.use_viewdirs) {
+            p.fold_tensor = (int)p.tensors.size();
+            size_t n_frag = 0, n_tile = 0;
+            auto copy_layer = [&](int tensor, int as_tensor) {          // a layer of frags16 / tiles16, re-labelled
+                for (; n_frag < (size_t)p.n_frags16_used && p.frags16[n_frag].tensor == tensor; ++n_frag) {
+                    FragDesc d = p.frags16[n_frag];
+                    d.tensor = as_tensor;
+                    p.frags16_fold.push_back(d);
+                }
+                for (; n_tile < p.tiles16.size() && p.tiles16[n_tile].tensor == tensor; ++n_tile)
+                    p.tiles16_fold.push_back({as_tensor, p.tiles16[n_tile].row0});
+            };
+            for (int i = 0; i < D; ++i) copy_layer(i, i);
+            while (n_frag < (size_t)p.n_frags16_used && p.frags16[n_frag].tensor == D) ++n_frag;      // feature: folded away
+            while (n_tile < p.tiles16.size() && p.tiles16[n_tile].tensor == D) ++n_tile;
+            copy_layer(D + 1, D + 1);                   // alpha
+            copy_layer(D + 2, p.fold_tensor);           // views over [W' | Wv[:, W:]]: same shape as views_linears.0
+            copy_layer(D + 3, D + 3);                   // rgb
+            p.n_frags16_fold_used = (int)p.frags16_fold.size();
+            while (p.frags16_fold.size() % STREAM_PAD_FRAGS) p.frags16_fold.push_back({0, FRAG_ZERO, 0, 0, 0, 0, 0, 0});
+        }
         p.n_frags_split_used = (int)p.frags_split.size();
         while (p.frags_split.size() % STREAM_PAD_FRAGS) p.frags_split.push_back({0, FRAG_ZERO, 0, 0, 0, 0, 0, 0});
 

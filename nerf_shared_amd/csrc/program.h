@@ -164,6 +164,15 @@ struct Program {
     std::vector<FragDesc> frags16;
     std::vector<TileDesc> tiles16;
     int n_frags16_used = 0;
+    // folded s16 program (view-branch models; inference only): feature_linear has no activation behind it, so
+    // views_linears.0 reads h8 through W' = Wv[:, :W] . Wf (and b' = Wv[:, :W] . bf + bv).  The s16 program without the
+    // feature layer; the views layer is {H16 over W', GEN16 over Wv[:, W:]}, both read from the FOLD tensor: index
+    // tensors.size() of the pack's tables, a per-model fp32 scratch [W/2][W + input_ch_views] (+ [W/2] bias) that
+    // fold_kernel (pack.hip) fills from the fp32 parameters in front of the pack.  Empty without a view branch.
+    std::vector<FragDesc> frags16_fold;
+    std::vector<TileDesc> tiles16_fold;
+    int n_frags16_fold_used = 0;
+    int fold_tensor = -1;            // index of the FOLD tensor in the pack's tensor table, -1: nothing to fold
     // split-precision stream (mlp_split.hip): the s16 program with every fragment as an fp16 (hi, lo) pair, ordered
     // layer -> pair of output tiles -> k-step -> part -> tile of the pair; the bias table is tiles16's
     std::vector<FragDesc> frags_split;

@@ -179,8 +179,11 @@ class Renderer(torch.nn.Module):
         prec = coarse_model._precision_code()
         if use_fine and fine_model._precision_code() != prec:
             prec = _lib.PREC_FP32
-        hc = coarse_model._model_handle(dev, _lib.COPY_OF[prec])      # only the packed copy this precision reads
-        hf = fine_model._model_handle(dev, _lib.COPY_OF[prec]) if use_fine else None
+        # only the packed copy this precision reads; a bf16 render also reads the folded stream (feature_linear folded into
+        # views_linears.0, include/nerf_amd.h NERF_AMD_COPY_BF16_FOLD), which only the calls that render ask for
+        copies = _lib.COPY_OF[prec] | (_lib.COPY_BF16_FOLD if prec == _lib.PREC_BF16 else 0)
+        hc = coarse_model._model_handle(dev, copies)
+        hf = fine_model._model_handle(dev, copies) if use_fine else None
         return hc, hf, self._cfg(prec), lib.nerf_amd_model_out_ch(hc)
 
     def _chunk_io(self, rays, cfg, out_ch, outs, pytest, ws=None, z_pre=None, t_rand_out=None):
