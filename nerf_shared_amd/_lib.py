@@ -35,6 +35,8 @@ EXPORTS = (
     "nerf_amd_field_backward", "nerf_amd_coarse_z", "nerf_amd_resample", "nerf_amd_get_rays_backward", "nerf_amd_to8b", "nerf_amd_ndc_rays_backward", "nerf_amd_adam_step", "nerf_amd_adam_step_device", "nerf_amd_img2mse", "nerf_amd_img2mse_backward", "nerf_amd_assemble_rays",
     "nerf_amd_rays_at_pixels", "nerf_amd_rays_at_pixels_backward", "nerf_amd_se3_transform", "nerf_amd_se3_transform_backward",
     "nerf_amd_field_backward_inputs",
+    "nerf_amd_se3_transform_batch", "nerf_amd_se3_transform_batch_backward", "nerf_amd_rays_at_pixels_batch",
+    "nerf_amd_rays_at_pixels_batch_backward", "nerf_amd_img2mse_each", "nerf_amd_img2mse_each_backward",
     "nerf_amd_density_arch", "nerf_amd_density", "nerf_amd_density_grad_fused", "nerf_amd_density_grad_workspace",
     "nerf_amd_density_value_grad",
     "nerf_amd_draw_pixels", "nerf_amd_interest_points_workspace", "nerf_amd_interest_points", "nerf_amd_dilate_mask",
@@ -127,6 +129,15 @@ def _load():
         "nerf_amd_se3_transform": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
         "nerf_amd_se3_transform_backward": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                                     c_void_p]),
+        "nerf_amd_se3_transform_batch": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_void_p]),
+        "nerf_amd_se3_transform_batch_backward": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_void_p,
+                                                          c_void_p, c_void_p, c_void_p]),
+        "nerf_amd_rays_at_pixels_batch": (c_int, [c_int32, c_int32, POINTER(c_double), c_void_p, c_int64, c_int32, c_int32, c_void_p,
+                                                  c_int64, c_void_p, c_void_p, c_void_p]),
+        "nerf_amd_rays_at_pixels_batch_backward": (c_int, [c_int32, c_int32, POINTER(c_double), c_void_p, c_int64, c_int32, c_void_p,
+                                                           c_void_p, c_void_p, c_void_p]),
+        "nerf_amd_img2mse_each": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_int32, c_void_p, c_void_p]),
+        "nerf_amd_img2mse_each_backward": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_int32, c_void_p, c_void_p, c_void_p]),
         "nerf_amd_draw_pixels": (c_int, [c_int64, c_int32, c_uint32, c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_int64, c_int32,
                                          c_void_p, c_void_p, c_void_p]),
         "nerf_amd_interest_points_workspace": (c_int64, [c_int32, c_int32]),

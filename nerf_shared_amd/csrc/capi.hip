@@ -1231,6 +1231,64 @@ int nerf_amd_se3_transform_backward(const float *w, const float *v, const float 
     return rc ? fail(rc, "se3_transform_backward launch failed") : NERF_AMD_OK;
 }
 
+// ---- multi-start pose estimation: B hypotheses per launch -----------------------------------------------------------
+static bool pose_batch_ok(int32_t B) { return B >= 1 && B <= POSE_BATCH_MAX; }
+
+int nerf_amd_se3_transform_batch(const float *w, const float *v, const float *theta, const float *x, int32_t x_stride, int32_t B,
+                                 float *T, void *stream) {
+    if (!w || !v || !theta || !x || !T || (x_stride != 0 && x_stride != 16)) return fail(NERF_AMD_EINVAL, "bad se3_transform_batch arguments");
+    if (!pose_batch_ok(B)) return fail(NERF_AMD_EINVAL, "se3_transform_batch: need 1 <= B <= 1024");
+    int rc = launch_se3_transform_batch(w, v, theta, x, x_stride, B, T, static_cast<hipStream_t>(stream));
+    return rc ? fail(rc, "se3_transform_batch launch failed") : NERF_AMD_OK;
+}
+
+int nerf_amd_se3_transform_batch_backward(const float *w, const float *v, const float *theta, const float *x, int32_t x_stride,
+                                          int32_t B, const float *g_T, float *g_w, float *g_v, float *g_theta, void *stream) {
+    if (!w || !v || !theta || !x || !g_T || !g_w || !g_v || !g_theta || (x_stride != 0 && x_stride != 16))
+        return fail(NERF_AMD_EINVAL, "bad se3_transform_batch_backward arguments");
+    if (!pose_batch_ok(B)) return fail(NERF_AMD_EINVAL, "se3_transform_batch_backward: need 1 <= B <= 1024");
+    int rc = launch_se3_transform_batch_bwd(w, v, theta, x, x_stride, B, g_T, g_w, g_v, g_theta, static_cast<hipStream_t>(stream));
+    return rc ? fail(rc, "se3_transform_batch_backward launch failed") : NERF_AMD_OK;
+}
+
+int nerf_amd_rays_at_pixels_batch(int32_t H, int32_t W, const double *K4, const float *c2w, int64_t c2w_pose_stride,
+                                  int32_t c2w_row_stride, int32_t B, const int32_t *pix, int64_t n, float *rays_o, float *rays_d,
+                                  void *stream) {
+    if (H < 1 || W < 1 || !K4 || !c2w || c2w_pose_stride < 0 || c2w_row_stride < 4 || n < 0 || (n > 0 && (!pix || !rays_o || !rays_d)))
+        return fail(NERF_AMD_EINVAL, "bad rays_at_pixels_batch arguments");
+    if (!pose_batch_ok(B)) return fail(NERF_AMD_EINVAL, "rays_at_pixels_batch: need 1 <= B <= 1024");
+    int rc = launch_rays_at_pixels_batch(K4, c2w, c2w_pose_stride, c2w_row_stride, B, pix, n, rays_o, rays_d,
+                                         static_cast<hipStream_t>(stream));
+    return rc ? fail(rc, "rays_at_pixels_batch launch failed") : NERF_AMD_OK;
+}
+
+int nerf_amd_rays_at_pixels_batch_backward(int32_t H, int32_t W, const double *K4, const int32_t *pix, int64_t n, int32_t B,
+                                           const float *g_rays_o, const float *g_rays_d, float *g_c2w, void *stream) {
+    if (H < 1 || W < 1 || !K4 || n < 0 || (n > 0 && !pix) || !g_c2w) return fail(NERF_AMD_EINVAL, "bad rays_at_pixels_batch_backward arguments");
+    if (!pose_batch_ok(B)) return fail(NERF_AMD_EINVAL, "rays_at_pixels_batch_backward: need 1 <= B <= 1024");
+    if (n > RAYS_AT_BWD_PER_BLOCK)
+        return fail(NERF_AMD_EINVAL, "rays_at_pixels_batch_backward: one block per hypothesis, n <= 16384");
+    int rc = launch_rays_at_pixels_batch_bwd(K4, pix, n, B, g_rays_o, g_rays_d, g_c2w, static_cast<hipStream_t>(stream));
+    return rc ? fail(rc, "rays_at_pixels_batch_backward launch failed") : NERF_AMD_OK;
+}
+
+int nerf_amd_img2mse_each(const float *x, const float *y, int64_t y_stride, int64_t m, int32_t B, float *out, void *stream) {
+    if (m < 1 || !x || !y || !out || (y_stride != 0 && y_stride != m)) return fail(NERF_AMD_EINVAL, "bad img2mse_each arguments");
+    if (!pose_batch_ok(B)) return fail(NERF_AMD_EINVAL, "img2mse_each: need 1 <= B <= 1024");
+    if (m > IMG2MSE_EACH_MAX) return fail(NERF_AMD_EINVAL, "img2mse_each: one block per hypothesis, m <= 16384");
+    int rc = launch_img2mse_each(x, y, y_stride, m, B, out, static_cast<hipStream_t>(stream));
+    return rc ? fail(rc, "img2mse_each launch failed") : NERF_AMD_OK;
+}
+
+int nerf_amd_img2mse_each_backward(const float *x, const float *y, int64_t y_stride, int64_t m, int32_t B, const float *g, float *gx,
+                                   void *stream) {
+    if (m < 1 || !x || !y || !g || !gx || (y_stride != 0 && y_stride != m)) return fail(NERF_AMD_EINVAL, "bad img2mse_each_backward arguments");
+    if (!pose_batch_ok(B)) return fail(NERF_AMD_EINVAL, "img2mse_each_backward: need 1 <= B <= 1024");
+    if (m > IMG2MSE_EACH_MAX) return fail(NERF_AMD_EINVAL, "img2mse_each_backward: one block per hypothesis, m <= 16384");
+    int rc = launch_img2mse_each_bwd(x, y, y_stride, m, B, g, gx, static_cast<hipStream_t>(stream));
+    return rc ? fail(rc, "img2mse_each_backward launch failed") : NERF_AMD_OK;
+}
+
 int nerf_amd_draw_pixels(int64_t M, int32_t n, uint32_t seed, int64_t *draw_count, const int32_t *region, int32_t H, int32_t W,
                          const float *image, int64_t row_stride, int32_t C, int32_t *pixels, float *target, void *stream) {
     if (H < 1 || W < 1 || C < 3 || row_stride < (int64_t)W * C || !draw_count || !image || !pixels || !target)

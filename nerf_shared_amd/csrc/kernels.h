@@ -202,6 +202,20 @@ int launch_rays_at_pixels_bwd(const double *K4, const int32_t *pix, int64_t n, c
 int launch_se3_transform(const float *w, const float *v, const float *theta, const float *x, float *T, hipStream_t s);
 int launch_se3_transform_bwd(const float *w, const float *v, const float *theta, const float *x, const float *g_T, float *g_w,
                              float *g_v, float *g_theta, hipStream_t s);
+// multi-start pose estimation: B hypotheses per launch, each slice bit-equal to the single-pose launcher above (shared
+// device bodies).  One block per hypothesis in the two reductions, hence their one-launch limits (EINVAL beyond).
+constexpr int POSE_BATCH_MAX = 1024, IMG2MSE_EACH_MAX = 16384;
+int launch_se3_transform_batch(const float *w, const float *v, const float *theta, const float *x, int x_stride, int B, float *T,
+                               hipStream_t s);
+int launch_se3_transform_batch_bwd(const float *w, const float *v, const float *theta, const float *x, int x_stride, int B,
+                                   const float *g_T, float *g_w, float *g_v, float *g_theta, hipStream_t s);
+int launch_rays_at_pixels_batch(const double *K4, const float *c2w, int64_t c2w_pose_stride, int c2w_row_stride, int B,
+                                const int32_t *pix, int64_t n, float *rays_o, float *rays_d, hipStream_t s);
+int launch_rays_at_pixels_batch_bwd(const double *K4, const int32_t *pix, int64_t n, int B, const float *g_o, const float *g_d,
+                                    float *g_c2w, hipStream_t s);
+int launch_img2mse_each(const float *x, const float *y, int64_t y_stride, int64_t m, int B, float *out, hipStream_t s);
+int launch_img2mse_each_bwd(const float *x, const float *y, int64_t y_stride, int64_t m, int B, const float *g, float *gx,
+                            hipStream_t s);
 // pixel selection for pose estimation (pixel_select.hip; demo_est_rel_pose.py:35-47, :75-79)
 int launch_draw_pixels(int64_t M, int n, uint32_t seed, int64_t *draw_count, const int32_t *region, int W, const float *image,
                        int64_t row_stride, int C, int32_t *pixels, float *target, hipStream_t s);

@@ -795,19 +795,33 @@ __device__ __forceinline__ float block_sum_1024(float v, float *part /* [16] LDS
     return t;                        // valid in thread 0
 }
 
-__global__ __launch_bounds__(MSE_BLOCK) void img2mse_kernel(const float *x, const float *y, int64_t n, float *out, float *partials) {
-    __shared__ float part[MSE_BLOCK / 64];
+// Block `block` of `n_blocks` of one mean((x - y)^2) over n values: the body of img2mse_kernel and of img2mse_each_kernel (which
+// runs it as block 0 of 1 per hypothesis -- the same loop, butterfly and wave-order sum, so the same bits).
+__device__ __forceinline__ void img2mse_block(const float *x, const float *y, int64_t n, float *out, float *partials, int block,
+                                              int n_blocks, float *part /* [16] LDS */) {
     float acc = 0.f;
-    const int64_t stride = (int64_t)gridDim.x * MSE_BLOCK;
-    for (int64_t i = (int64_t)blockIdx.x * MSE_BLOCK + threadIdx.x; i < n; i += stride) {
+    const int64_t stride = (int64_t)n_blocks * MSE_BLOCK;
+    for (int64_t i = (int64_t)block * MSE_BLOCK + threadIdx.x; i < n; i += stride) {
         const float d = x[i] - y[i];
         acc += d * d;
     }
     const float t = block_sum_1024(acc, part);
     if (threadIdx.x == 0) {
-        if (gridDim.x == 1) out[0] = t / (float)n;
-        else partials[blockIdx.x] = t;
+        if (n_blocks == 1) out[0] = t / (float)n;
+        else partials[block] = t;
     }
+}
+
+__global__ __launch_bounds__(MSE_BLOCK) void img2mse_kernel(const float *x, const float *y, int64_t n, float *out, float *partials) {
+    __shared__ float part[MSE_BLOCK / 64];
+    img2mse_block(x, y, n, out, partials, (int)blockIdx.x, (int)gridDim.x, part);
+}
+
+// One loss per hypothesis: block b is img2mse_kernel's single-block path on x[b], y_b.
+__global__ __launch_bounds__(MSE_BLOCK) void img2mse_each_kernel(const float *x, const float *y, int64_t y_stride, int64_t m, float *out) {
+    __shared__ float part[MSE_BLOCK / 64];
+    const int64_t b = blockIdx.x;
+    img2mse_block(x + b * m, y + b * y_stride, m, out + b, nullptr, 0, 1, part);
 }
 
 __global__ __launch_bounds__(MSE_MAX_BLOCKS) void img2mse_finish_kernel(const float *partials, int n_parts, int64_t n, float *out) {
@@ -821,7 +835,8 @@ __global__ __launch_bounds__(MSE_MAX_BLOCKS) void img2mse_finish_kernel(const fl
     }
 }
 
-__global__ __launch_bounds__(256) void img2mse_bwd_kernel(const float *x, const float *y, int64_t n, const float *g, float *gx, float *gy) {
+// gx = g[0] * 2 (x - y) / n, gy = -gx over the grid's x dimension: the body of img2mse_bwd_kernel and img2mse_each_bwd_kernel.
+__device__ __forceinline__ void img2mse_bwd_body(const float *x, const float *y, int64_t n, const float *g, float *gx, float *gy) {
     const float s = g[0] * (2.0f / (float)n);
     const int64_t stride = (int64_t)gridDim.x * 256;
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += stride) {
@@ -829,6 +844,17 @@ __global__ __launch_bounds__(256) void img2mse_bwd_kernel(const float *x, const 
         if (gx) gx[i] = v;
         if (gy) gy[i] = -v;
     }
+}
+
+__global__ __launch_bounds__(256) void img2mse_bwd_kernel(const float *x, const float *y, int64_t n, const float *g, float *gx, float *gy) {
+    img2mse_bwd_body(x, y, n, g, gx, gy);
+}
+
+// grid (blocks over m, B): row blockIdx.y is img2mse_bwd_kernel on x[b], y_b with the scalar g[b].
+__global__ __launch_bounds__(256) void img2mse_each_bwd_kernel(const float *x, const float *y, int64_t y_stride, int64_t m, const float *g,
+                                                               float *gx) {
+    const int64_t b = blockIdx.y;
+    img2mse_bwd_body(x + b * m, y + b * y_stride, m, g + b, gx + b * m, nullptr);
 }
 
 int launch_img2mse(const float *x, const float *y, int64_t n, float *out, float *partials, hipStream_t s) {
@@ -846,6 +872,20 @@ int launch_img2mse_bwd(const float *x, const float *y, int64_t n, const float *g
     int64_t blocks = (n + 1023) / 1024;
     if (blocks > 2048) blocks = 2048;
     hipLaunchKernelGGL(img2mse_bwd_kernel, dim3((unsigned)blocks), dim3(256), 0, s, x, y, n, g, gx, gy);
+    return hipGetLastError() == hipSuccess ? NERF_AMD_OK : NERF_AMD_EHIP;
+}
+
+int launch_img2mse_each(const float *x, const float *y, int64_t y_stride, int64_t m, int B, float *out, hipStream_t s) {
+    if (B < 1 || B > POSE_BATCH_MAX || m < 1 || m > IMG2MSE_EACH_MAX) return NERF_AMD_EINVAL;
+    static_assert(IMG2MSE_EACH_MAX == MSE_PER_BLOCK, "img2mse_each is img2mse's one-block path");
+    hipLaunchKernelGGL(img2mse_each_kernel, dim3((unsigned)B), dim3(MSE_BLOCK), 0, s, x, y, y_stride, m, out);
+    return hipGetLastError() == hipSuccess ? NERF_AMD_OK : NERF_AMD_EHIP;
+}
+
+int launch_img2mse_each_bwd(const float *x, const float *y, int64_t y_stride, int64_t m, int B, const float *g, float *gx,
+                            hipStream_t s) {
+    if (B < 1 || B > POSE_BATCH_MAX || m < 1 || m > IMG2MSE_EACH_MAX) return NERF_AMD_EINVAL;
+    hipLaunchKernelGGL(img2mse_each_bwd_kernel, dim3((unsigned)((m + 1023) / 1024), (unsigned)B), dim3(256), 0, s, x, y, y_stride, m, g, gx);
     return hipGetLastError() == hipSuccess ? NERF_AMD_OK : NERF_AMD_EHIP;
 }
 
@@ -894,10 +934,8 @@ struct PixCam { float fx, fy, cx, cy; };
 
 // make_rays_kernel's arithmetic for pixel (x, y) = pix[idx]: the same operations in the same order, so the result equals
 // get_rays(...)[y, x] bit for bit.  One thread per ray; the 12 pose values are loaded (uniformly) by every thread.
-__global__ __launch_bounds__(256) void rays_at_pixels_kernel(PixCam k, const float *c2w, int stride, const int32_t *pix, int64_t n,
-                                                             float *rays_o, float *rays_d) {
-    const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (idx >= n) return;
+__device__ __forceinline__ void ray_at_pixel(PixCam k, const float *c2w, int stride, const int32_t *pix, int64_t idx, float *rays_o,
+                                             float *rays_d) {
     float c[12];
 #pragma unroll
     for (int r = 0; r < 3; ++r)
@@ -911,11 +949,36 @@ __global__ __launch_bounds__(256) void rays_at_pixels_kernel(PixCam k, const flo
     rays_d[3 * idx] = d[0]; rays_d[3 * idx + 1] = d[1]; rays_d[3 * idx + 2] = d[2];
 }
 
+__global__ __launch_bounds__(256) void rays_at_pixels_kernel(PixCam k, const float *c2w, int stride, const int32_t *pix, int64_t n,
+                                                             float *rays_o, float *rays_d) {
+    const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx >= n) return;
+    ray_at_pixel(k, c2w, stride, pix, idx, rays_o, rays_d);
+}
+
+// B poses at the same n pixels: grid (blocks over n, B), one thread per (b, pixel); rays_o / rays_d [B, n, 3].
+__global__ __launch_bounds__(256) void rays_at_pixels_batch_kernel(PixCam k, const float *c2w, int64_t pose_stride, int stride,
+                                                                   const int32_t *pix, int64_t n, float *rays_o, float *rays_d) {
+    const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x, b = blockIdx.y;
+    if (idx >= n) return;
+    ray_at_pixel(k, c2w + b * pose_stride, stride, pix, idx, rays_o + b * n * 3, rays_d + b * n * 3);
+}
+
 int launch_rays_at_pixels(const double *K4, const float *c2w, int c2w_stride, const int32_t *pix, int64_t n, float *rays_o,
                           float *rays_d, hipStream_t s) {
     if (n <= 0) return NERF_AMD_OK;
     const PixCam k = {(float)K4[0], (float)K4[1], (float)K4[2], (float)K4[3]};
     hipLaunchKernelGGL(rays_at_pixels_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, k, c2w, c2w_stride, pix, n, rays_o, rays_d);
+    return hipGetLastError() == hipSuccess ? NERF_AMD_OK : NERF_AMD_EHIP;
+}
+
+int launch_rays_at_pixels_batch(const double *K4, const float *c2w, int64_t c2w_pose_stride, int c2w_row_stride, int B,
+                                const int32_t *pix, int64_t n, float *rays_o, float *rays_d, hipStream_t s) {
+    if (B < 1 || B > POSE_BATCH_MAX) return NERF_AMD_EINVAL;
+    if (n <= 0) return NERF_AMD_OK;
+    const PixCam k = {(float)K4[0], (float)K4[1], (float)K4[2], (float)K4[3]};
+    hipLaunchKernelGGL(rays_at_pixels_batch_kernel, dim3((unsigned)((n + 255) / 256), (unsigned)B), dim3(256), 0, s, k, c2w,
+                       c2w_pose_stride, c2w_row_stride, pix, n, rays_o, rays_d);
     return hipGetLastError() == hipSuccess ? NERF_AMD_OK : NERF_AMD_EHIP;
 }
 
@@ -925,14 +988,15 @@ int launch_rays_at_pixels(const double *K4, const float *c2w, int c2w_stride, co
 // The loop is grid-strided, so any grid covers any n: RAYS_AT_BWD_PER_BLOCK (kernels.h) only chooses how many blocks are
 // launched (<= RAYS_AT_BWD_MAX_BLOCKS = the rows of `partials`) and need not be a multiple of the block size.
 constexpr int RAP_BLOCK = 1024;
-__global__ __launch_bounds__(RAP_BLOCK) void rays_at_pixels_bwd_kernel(PixCam k, const int32_t *pix, int64_t n, const float *g_o,
-                                                                       const float *g_d, float *g_c2w, float *partials) {
-    __shared__ float part[RAP_BLOCK / 64][12];
+// Block `block` of `n_blocks`: the body of rays_at_pixels_bwd_kernel and of rays_at_pixels_batch_bwd_kernel (block 0 of 1 per hypothesis).
+__device__ __forceinline__ void rays_at_pixels_bwd_block(PixCam k, const int32_t *pix, int64_t n, const float *g_o, const float *g_d,
+                                                         float *g_c2w, float *partials, int block, int n_blocks,
+                                                         float (*part)[12] /* [RAP_BLOCK / 64][12] LDS */) {
     float acc[12];
 #pragma unroll
     for (int i = 0; i < 12; ++i) acc[i] = 0.f;
-    const int64_t stride = (int64_t)gridDim.x * RAP_BLOCK;
-    for (int64_t idx = (int64_t)blockIdx.x * RAP_BLOCK + threadIdx.x; idx < n; idx += stride) {
+    const int64_t stride = (int64_t)n_blocks * RAP_BLOCK;
+    for (int64_t idx = (int64_t)block * RAP_BLOCK + threadIdx.x; idx < n; idx += stride) {
         const float i = (float)pix[2 * idx], j = (float)pix[2 * idx + 1];
         const float dir[3] = {(i - k.cx) / k.fx, -(j - k.cy) / k.fy, -1.0f};
 #pragma unroll
@@ -953,9 +1017,24 @@ __global__ __launch_bounds__(RAP_BLOCK) void rays_at_pixels_bwd_kernel(PixCam k,
         float t = 0.f;
 #pragma unroll
         for (int w = 0; w < RAP_BLOCK / 64; ++w) t += part[w][threadIdx.x];
-        if (gridDim.x == 1) g_c2w[threadIdx.x] = t;
-        else partials[blockIdx.x * 12 + threadIdx.x] = t;
+        if (n_blocks == 1) g_c2w[threadIdx.x] = t;
+        else partials[block * 12 + threadIdx.x] = t;
     }
+}
+
+__global__ __launch_bounds__(RAP_BLOCK) void rays_at_pixels_bwd_kernel(PixCam k, const int32_t *pix, int64_t n, const float *g_o,
+                                                                       const float *g_d, float *g_c2w, float *partials) {
+    __shared__ float part[RAP_BLOCK / 64][12];
+    rays_at_pixels_bwd_block(k, pix, n, g_o, g_d, g_c2w, partials, (int)blockIdx.x, (int)gridDim.x, part);
+}
+
+// One block per hypothesis: the one-launch path above over hypothesis b's n rays (g_o / g_d [B, n, 3], g_c2w [B, 12]).
+__global__ __launch_bounds__(RAP_BLOCK) void rays_at_pixels_batch_bwd_kernel(PixCam k, const int32_t *pix, int64_t n, const float *g_o,
+                                                                             const float *g_d, float *g_c2w) {
+    __shared__ float part[RAP_BLOCK / 64][12];
+    const int64_t b = blockIdx.x;
+    rays_at_pixels_bwd_block(k, pix, n, g_o ? g_o + b * n * 3 : nullptr, g_d ? g_d + b * n * 3 : nullptr, g_c2w + b * 12, nullptr, 0, 1,
+                             part);
 }
 
 __global__ __launch_bounds__(64) void rays_at_pixels_bwd_finish_kernel(const float *partials, int n_parts, float *g_c2w) {
@@ -974,6 +1053,15 @@ int launch_rays_at_pixels_bwd(const double *K4, const int32_t *pix, int64_t n, c
     const PixCam k = {(float)K4[0], (float)K4[1], (float)K4[2], (float)K4[3]};
     hipLaunchKernelGGL(rays_at_pixels_bwd_kernel, dim3((unsigned)blocks), dim3(RAP_BLOCK), 0, s, k, pix, n, g_o, g_d, g_c2w, partials);
     if (blocks > 1) hipLaunchKernelGGL(rays_at_pixels_bwd_finish_kernel, dim3(1), dim3(64), 0, s, partials, (int)blocks, g_c2w);
+    return hipGetLastError() == hipSuccess ? NERF_AMD_OK : NERF_AMD_EHIP;
+}
+
+int launch_rays_at_pixels_batch_bwd(const double *K4, const int32_t *pix, int64_t n, int B, const float *g_o, const float *g_d,
+                                    float *g_c2w, hipStream_t s) {
+    if (B < 1 || B > POSE_BATCH_MAX || n > RAYS_AT_BWD_PER_BLOCK) return NERF_AMD_EINVAL;
+    if (n <= 0) return hipMemsetAsync(g_c2w, 0, (size_t)B * 12 * sizeof(float), s) == hipSuccess ? NERF_AMD_OK : NERF_AMD_EHIP;
+    const PixCam k = {(float)K4[0], (float)K4[1], (float)K4[2], (float)K4[3]};
+    hipLaunchKernelGGL(rays_at_pixels_batch_bwd_kernel, dim3((unsigned)B), dim3(RAP_BLOCK), 0, s, k, pix, n, g_o, g_d, g_c2w);
     return hipGetLastError() == hipSuccess ? NERF_AMD_OK : NERF_AMD_EHIP;
 }
 
@@ -1008,8 +1096,7 @@ __device__ __forceinline__ Se3 se3_load(const float *w, const float *v, const fl
     return e;
 }
 
-__global__ __launch_bounds__(64) void se3_transform_kernel(const float *w, const float *v, const float *theta, const float *x, float *T) {
-    if (threadIdx.x != 0) return;
+__device__ __forceinline__ void se3_forward(const float *w, const float *v, const float *theta, const float *x, float *T) {
     const Se3 e = se3_load(w, v, theta);
     double E[4][4];
     for (int i = 0; i < 3; ++i) {
@@ -1030,14 +1117,26 @@ __global__ __launch_bounds__(64) void se3_transform_kernel(const float *w, const
         }
 }
 
+__global__ __launch_bounds__(64) void se3_transform_kernel(const float *w, const float *v, const float *theta, const float *x, float *T) {
+    if (threadIdx.x != 0) return;
+    se3_forward(w, v, theta, x, T);
+}
+
+// B hypotheses, one lane each (lane b of the grid's waves): w, v [B, 3], theta [B], x at b * x_stride (0 = shared), T [B, 16].
+__global__ __launch_bounds__(64) void se3_transform_batch_kernel(const float *w, const float *v, const float *theta, const float *x,
+                                                                 int x_stride, int B, float *T) {
+    const int b = blockIdx.x * 64 + threadIdx.x;
+    if (b >= B) return;
+    se3_forward(w + 3 * b, v + 3 * b, theta + b, x + b * x_stride, T + 16 * b);
+}
+
 // dL/d(w, v, theta) from g_T: g_E = g_T x^T (rows 0..2), G_R = g_E[:, :3], g_u = g_E[:, 3], G_A = g_u v^T;
 //   g_v  = A^T g_u
 //   g_th = <G_R, cos K + sin K^2> + <G_A, I + sin K + (1 - cos) K^2>
 //   G_K  = sin G_R + (1 - cos)(G_R K^T + K^T G_R) + (1 - cos) G_A + (th - sin)(G_A K^T + K^T G_A)
 //   g_w  = (G_K[2][1] - G_K[1][2], G_K[0][2] - G_K[2][0], G_K[1][0] - G_K[0][1])
-__global__ __launch_bounds__(64) void se3_transform_bwd_kernel(const float *w, const float *v, const float *theta, const float *x,
-                                                               const float *g_T, float *g_w, float *g_v, float *g_theta) {
-    if (threadIdx.x != 0) return;
+__device__ __forceinline__ void se3_backward(const float *w, const float *v, const float *theta, const float *x, const float *g_T,
+                                             float *g_w, float *g_v, float *g_theta) {
     const Se3 e = se3_load(w, v, theta);
     double GR[3][3], gu[3], GA[3][3];
     for (int i = 0; i < 3; ++i)
@@ -1068,6 +1167,20 @@ __global__ __launch_bounds__(64) void se3_transform_bwd_kernel(const float *w, c
     g_theta[0] = (float)gth;
 }
 
+__global__ __launch_bounds__(64) void se3_transform_bwd_kernel(const float *w, const float *v, const float *theta, const float *x,
+                                                               const float *g_T, float *g_w, float *g_v, float *g_theta) {
+    if (threadIdx.x != 0) return;
+    se3_backward(w, v, theta, x, g_T, g_w, g_v, g_theta);
+}
+
+__global__ __launch_bounds__(64) void se3_transform_batch_bwd_kernel(const float *w, const float *v, const float *theta, const float *x,
+                                                                     int x_stride, int B, const float *g_T, float *g_w, float *g_v,
+                                                                     float *g_theta) {
+    const int b = blockIdx.x * 64 + threadIdx.x;
+    if (b >= B) return;
+    se3_backward(w + 3 * b, v + 3 * b, theta + b, x + b * x_stride, g_T + 16 * b, g_w + 3 * b, g_v + 3 * b, g_theta + b);
+}
+
 int launch_se3_transform(const float *w, const float *v, const float *theta, const float *x, float *T, hipStream_t s) {
     hipLaunchKernelGGL(se3_transform_kernel, dim3(1), dim3(64), 0, s, w, v, theta, x, T);
     return hipGetLastError() == hipSuccess ? NERF_AMD_OK : NERF_AMD_EHIP;
@@ -1076,6 +1189,21 @@ int launch_se3_transform(const float *w, const float *v, const float *theta, con
 int launch_se3_transform_bwd(const float *w, const float *v, const float *theta, const float *x, const float *g_T, float *g_w,
                              float *g_v, float *g_theta, hipStream_t s) {
     hipLaunchKernelGGL(se3_transform_bwd_kernel, dim3(1), dim3(64), 0, s, w, v, theta, x, g_T, g_w, g_v, g_theta);
+    return hipGetLastError() == hipSuccess ? NERF_AMD_OK : NERF_AMD_EHIP;
+}
+
+int launch_se3_transform_batch(const float *w, const float *v, const float *theta, const float *x, int x_stride, int B, float *T,
+                               hipStream_t s) {
+    if (B < 1 || B > POSE_BATCH_MAX || (x_stride != 0 && x_stride != 16)) return NERF_AMD_EINVAL;
+    hipLaunchKernelGGL(se3_transform_batch_kernel, dim3((unsigned)((B + 63) / 64)), dim3(64), 0, s, w, v, theta, x, x_stride, B, T);
+    return hipGetLastError() == hipSuccess ? NERF_AMD_OK : NERF_AMD_EHIP;
+}
+
+int launch_se3_transform_batch_bwd(const float *w, const float *v, const float *theta, const float *x, int x_stride, int B,
+                                   const float *g_T, float *g_w, float *g_v, float *g_theta, hipStream_t s) {
+    if (B < 1 || B > POSE_BATCH_MAX || (x_stride != 0 && x_stride != 16)) return NERF_AMD_EINVAL;
+    hipLaunchKernelGGL(se3_transform_batch_bwd_kernel, dim3((unsigned)((B + 63) / 64)), dim3(64), 0, s, w, v, theta, x, x_stride, B, g_T,
+                       g_w, g_v, g_theta);
     return hipGetLastError() == hipSuccess ? NERF_AMD_OK : NERF_AMD_EHIP;
 }
 

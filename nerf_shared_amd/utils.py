@@ -57,6 +57,49 @@ def img2mse(x, y):
     return torch.mean((x - y) ** 2)
 
 
+class _Img2MseEachFn(torch.autograd.Function):
+    """out[b] = mean((x[b] - y_b)^2) (nerf_amd_img2mse_each): one block per hypothesis, one launch each way; y is a constant."""
+
+    @staticmethod
+    def forward(ctx, x, y):
+        dev, B = x.device, x.shape[0]
+        m = x.numel() // B
+        out = torch.empty(B, device=dev, dtype=torch.float32)
+        ctx.y_stride = m if y.dim() == x.dim() else 0
+        with torch.cuda.device(dev):
+            _lib.check(lib.nerf_amd_img2mse_each(x.data_ptr(), y.data_ptr(), ctx.y_stride, m, B, out.data_ptr(), _lib.stream_of(dev)),
+                       "nerf_amd_img2mse_each")
+        ctx.save_for_backward(x, y)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        x, y = ctx.saved_tensors
+        dev, B = x.device, x.shape[0]
+        gx = torch.empty_like(x)
+        g = g.contiguous().float()
+        with torch.cuda.device(dev):
+            _lib.check(lib.nerf_amd_img2mse_each_backward(x.data_ptr(), y.data_ptr(), ctx.y_stride, x.numel() // B, B, g.data_ptr(),
+                                                          gx.data_ptr(), _lib.stream_of(dev)), "nerf_amd_img2mse_each_backward")
+        return gx, None
+
+
+POSE_BATCH_MAX, IMG2MSE_EACH_MAX = 1024, 16384          # csrc/kernels.h: hypotheses per launch, values per one-block loss
+
+
+def img2mse_each(x, y):
+    """One img2mse per hypothesis: x [B, ...], y of the same shape or of the shape of one x[b] (shared by all) -> [B], each
+    entry bit-equal to img2mse(x[b], y_b).  fp32 contiguous tensors on one ROCm device with B <= 1024 and at most 16384
+    values per hypothesis go through the library (one block per hypothesis, one launch each way; y is a constant there);
+    anything else is ((x - y) ** 2).flatten(1).mean(1)."""
+    if (isinstance(x, torch.Tensor) and isinstance(y, torch.Tensor) and x.is_cuda and y.is_cuda and x.device == y.device
+            and x.dtype == torch.float32 and y.dtype == torch.float32 and x.dim() >= 2 and 1 <= x.shape[0] <= POSE_BATCH_MAX
+            and (y.shape == x.shape or y.shape == x.shape[1:]) and 1 <= x[0].numel() <= IMG2MSE_EACH_MAX
+            and x.is_contiguous() and y.is_contiguous() and not (y.requires_grad and torch.is_grad_enabled())):
+        return _Img2MseEachFn.apply(x, y)
+    return ((x - y) ** 2).flatten(1).mean(1)
+
+
 mse2psnr = lambda x: -10. * torch.log(x) / torch.log(torch.Tensor([10.]).to(x.device))  # noqa: E731
 
 
@@ -182,6 +225,41 @@ class _RaysAtPixelsFn(torch.autograd.Function):
         return g, None, None, None, None
 
 
+class _RaysAtPixelsBatchFn(torch.autograd.Function):
+    """get_rays_at for B poses at shared pixels (nerf_amd_rays_at_pixels_batch and its backward, one block per hypothesis)."""
+
+    @staticmethod
+    def forward(ctx, c2w, pix, H, W, K4):
+        dev, B, n = c2w.device, c2w.shape[0], pix.shape[0]
+        o, d = torch.empty(B, n, 3, device=dev, dtype=torch.float32), torch.empty(B, n, 3, device=dev, dtype=torch.float32)
+        k4 = (ctypes.c_double * 4)(*K4)
+        with torch.cuda.device(dev):
+            _lib.check(lib.nerf_amd_rays_at_pixels_batch(H, W, k4, c2w.data_ptr(), c2w.stride(0), c2w.stride(1), B, pix.data_ptr(), n,
+                                                         o.data_ptr(), d.data_ptr(), _lib.stream_of(dev)), "nerf_amd_rays_at_pixels_batch")
+        ctx.meta = (H, W, K4, tuple(c2w.shape))
+        ctx.pix = pix
+        return o, d
+
+    @staticmethod
+    def backward(ctx, g_o, g_d):
+        H, W, K4, shape = ctx.meta
+        pix = ctx.pix
+        dev, n, B = pix.device, pix.shape[0], shape[0]
+        g_o = None if g_o is None else g_o.contiguous().float()
+        g_d = None if g_d is None else g_d.contiguous().float()
+        out = torch.empty(B, 3, 4, device=dev, dtype=torch.float32)
+        k4 = (ctypes.c_double * 4)(*K4)
+        with torch.cuda.device(dev):
+            _lib.check(lib.nerf_amd_rays_at_pixels_batch_backward(H, W, k4, pix.data_ptr(), n, B, _lib.ptr(g_o), _lib.ptr(g_d),
+                                                                  out.data_ptr(), _lib.stream_of(dev)),
+                       "nerf_amd_rays_at_pixels_batch_backward")
+        if shape[1] > 3:                           # row 3 of a [4, 4] pose gets no gradient
+            g = torch.zeros(shape, device=dev, dtype=torch.float32)
+            g[:, :3] = out
+            out = g
+        return out, None, None, None, None
+
+
 def _device_pixels(pixels, H, W, device):
     """[n, 2] int32 (x, y) on `device`.  Host pixels (list, array, CPU tensor) are checked against the image; a device
     tensor is converted there and trusted."""
@@ -207,9 +285,22 @@ def get_rays_at(H, W, K, c2w, pixels):
     `pixels`: an integer device tensor (int32, or int64 converted on the device), or host integers (list, array, CPU
     tensor).  Host pixels outside the image raise NerfAmdError.  A DEVICE tensor is TRUSTED: checking it would need a
     synchronisation.  (Out-of-range values are harmless to memory -- a pixel only enters arithmetic -- and give the ray
-    of that off-image position.)"""
+    of that off-image position.)
+
+    B poses at once: c2w [B, 3, 4] or [B, 4, 4] (B <= 1024) gives rays_o, rays_d [B, n, 3] at the SAME pixels, slice b
+    bit-equal to get_rays_at(H, W, K, c2w[b], pixels); the backward is one block per hypothesis (n <= 16384)."""
     if not (isinstance(c2w, torch.Tensor) and c2w.is_cuda):
         raise _lib.NerfAmdError("get_rays_at reads the pose on the device: c2w must be a ROCm tensor (utils.get_rays takes host poses)")
+    if c2w.dim() == 3:
+        if c2w.shape[1] not in (3, 4) or c2w.shape[2] != 4 or not 1 <= c2w.shape[0] <= POSE_BATCH_MAX:
+            raise _lib.NerfAmdError("a pose batch must be [B, 3, 4] or [B, 4, 4] with 1 <= B <= %d, got %s" % (POSE_BATCH_MAX, tuple(c2w.shape)))
+        pose = c2w if (c2w.dtype == torch.float32 and c2w.stride(2) == 1 and c2w.stride(1) >= 4 and c2w.stride(0) >= 0) \
+            else c2w.float().contiguous()
+        pix = _device_pixels(pixels, int(H), int(W), pose.device)
+        K4 = (float(K[0][0]), float(K[1][1]), float(K[0][2]), float(K[1][2]))
+        if not (pose.requires_grad and torch.is_grad_enabled()):
+            pose = pose.detach()
+        return _RaysAtPixelsBatchFn.apply(pose, pix, int(H), int(W), K4)
     if c2w.dim() != 2 or c2w.shape[0] not in (3, 4) or c2w.shape[1] != 4:
         raise _lib.NerfAmdError("c2w must be [3, 4] or [4, 4], got %s" % (tuple(c2w.shape),))
     pose = c2w if (c2w.dtype == torch.float32 and c2w.stride(1) == 1 and c2w.stride(0) >= 4) else c2w.float().contiguous()
@@ -269,6 +360,73 @@ class CameraTransf(torch.nn.Module):
         if any(p.dtype != torch.float32 or p.device != x.device for p in (self.w, self.v, self.theta)):
             raise _lib.NerfAmdError("CameraTransf's parameters must be fp32 on the pose's device (%s)" % x.device)
         return _Se3Fn.apply(self.w, self.v, self.theta, x.detach().float().contiguous())
+
+
+class _Se3BatchFn(torch.autograd.Function):
+    """T[b] = exp_i(w[b], v[b], theta[b]) x_b (nerf_amd_se3_transform_batch): one launch each way; x is a constant."""
+
+    @staticmethod
+    def forward(ctx, w, v, theta, x):
+        B = w.shape[0]
+        T = torch.empty(B, 4, 4, device=x.device, dtype=torch.float32)
+        ctx.x_stride = 16 if x.dim() == 3 else 0
+        with torch.cuda.device(x.device):
+            _lib.check(lib.nerf_amd_se3_transform_batch(w.data_ptr(), v.data_ptr(), theta.data_ptr(), x.data_ptr(), ctx.x_stride, B,
+                                                        T.data_ptr(), _lib.stream_of(x.device)), "nerf_amd_se3_transform_batch")
+        ctx.save_for_backward(w, v, theta, x)
+        return T
+
+    @staticmethod
+    def backward(ctx, g_T):
+        w, v, theta, x = ctx.saved_tensors
+        B = w.shape[0]
+        g = torch.empty(7 * B, device=x.device, dtype=torch.float32)
+        g_T = g_T.contiguous().float()
+        with torch.cuda.device(x.device):
+            _lib.check(lib.nerf_amd_se3_transform_batch_backward(w.data_ptr(), v.data_ptr(), theta.data_ptr(), x.data_ptr(), ctx.x_stride,
+                                                                 B, g_T.data_ptr(), g.data_ptr(), g.data_ptr() + 12 * B,
+                                                                 g.data_ptr() + 24 * B, _lib.stream_of(x.device)),
+                       "nerf_amd_se3_transform_batch_backward")
+        return g[:3 * B].view(B, 3), g[3 * B:6 * B].view(B, 3), g[6 * B:], None
+
+
+class CameraTransfBatch(torch.nn.Module):
+    """n_poses CameraTransf modules in one: w [B, 3], v [B, 3], theta [B] (normal(0, 1e-6) like CameraTransf; state_dict keys
+    w, v, theta), T[b] = exp_i(w[b], v[b], theta[b]) @ x_b.  forward(x) takes one start pose [4, 4] shared by all hypotheses
+    or [B, 4, 4] and returns [B, 4, 4]; row b is bit-equal to a CameraTransf with row b's parameters, forward and backward
+    (one launch each, one lane per hypothesis).  x is a constant.  This is the module of multi-start pose estimation
+    (CapturedMultiPoseStep): Adam is elementwise, so one optim.Adam over the three tensors is B independent Adams."""
+
+    def __init__(self, n_poses):
+        super().__init__()
+        B = int(n_poses)
+        if not 1 <= B <= POSE_BATCH_MAX:
+            raise _lib.NerfAmdError("CameraTransfBatch holds 1..%d poses, got %d" % (POSE_BATCH_MAX, B))
+        self.w = torch.nn.Parameter(torch.normal(0., 1e-6, size=(B, 3)))
+        self.v = torch.nn.Parameter(torch.normal(0., 1e-6, size=(B, 3)))
+        self.theta = torch.nn.Parameter(torch.normal(0., 1e-6, size=(B,)))
+
+    @property
+    def n_poses(self):
+        return self.w.shape[0]
+
+    def forward(self, x):
+        B = self.n_poses
+        _lib.require_device(x, "x")
+        _lib.require_device(self.w, "CameraTransfBatch's parameters")
+        if tuple(x.shape) not in ((4, 4), (B, 4, 4)):
+            raise _lib.NerfAmdError("CameraTransfBatch(%d) takes a [4, 4] or [%d, 4, 4] pose, got %s" % (B, B, tuple(x.shape)))
+        if any(p.dtype != torch.float32 or p.device != x.device or not p.is_contiguous() for p in (self.w, self.v, self.theta)):
+            raise _lib.NerfAmdError("CameraTransfBatch's parameters must be contiguous fp32 on the pose's device (%s)" % x.device)
+        return _Se3BatchFn.apply(self.w, self.v, self.theta, x.detach().float().contiguous())
+
+    def pose_module(self, b):
+        """A CameraTransf holding COPIES of hypothesis b's seven numbers (on their device): the way to go on with the winner
+        alone in a CapturedPoseStep."""
+        m = CameraTransf().to(self.w.device)
+        with torch.no_grad():
+            m.w.copy_(self.w[b]); m.v.copy_(self.v[b]); m.theta.copy_(self.theta[b])
+        return m
 
 
 # ---------------------------------------------------------------- which pixels a pose-estimation step looks at
@@ -697,24 +855,24 @@ class CapturedPoseStep:
     def __init__(self, renderer, H, W, K, chunk, coarse_model, fine_model, cam_transf, start_pose, optimizer, n_rays, warmup=3,
                  sampler=None):
         from . import optim
+        me = type(self).__name__                  # (CapturedMultiPoseStep shares this constructor)
         if not isinstance(optimizer, optim.Adam):
-            raise _lib.NerfAmdError("CapturedPoseStep needs nerf_shared_amd.optim.Adam over cam_transf.parameters(): torch's "
-                                    "optimizers pass step-dependent scalars as kernel arguments, which a graph would freeze")
+            raise _lib.NerfAmdError("%s needs nerf_shared_amd.optim.Adam over cam_transf.parameters(): torch's "
+                                    "optimizers pass step-dependent scalars as kernel arguments, which a graph would freeze" % me)
         for name, m in (("coarse_model", coarse_model), ("fine_model", fine_model)):
             if m is not None and any(p.requires_grad for p in m.parameters()):
-                raise _lib.NerfAmdError("CapturedPoseStep optimises the pose against FROZEN fields: call %s.requires_grad_(False) "
-                                        "(its parameters ask for gradients that this step would compute and nobody would use)" % name)
+                raise _lib.NerfAmdError("%s optimises the pose against FROZEN fields: call %s.requires_grad_(False) "
+                                        "(its parameters ask for gradients that this step would compute and nobody would use)" % (me, name))
         self.params = [p for g in optimizer.param_groups for p in g["params"]]
         mine = {id(p) for p in cam_transf.parameters()}
         if not self.params or {id(p) for p in self.params} != mine:
-            raise _lib.NerfAmdError("CapturedPoseStep: the optimizer must hold exactly cam_transf's parameters (w, v, theta)")
+            raise _lib.NerfAmdError("%s: the optimizer must hold exactly cam_transf's parameters (w, v, theta)" % me)
         dev = self.params[0].device
         _lib.require_device(self.params[0], "cam_transf's parameters")
         self.renderer, self.models, self.cam_transf, self.optimizer = renderer, (coarse_model, fine_model), cam_transf, optimizer
         self.args = (int(H), int(W), K, chunk)
         self.start_pose = torch.as_tensor(start_pose, dtype=torch.float32).to(dev).contiguous().clone()
-        if tuple(self.start_pose.shape) != (4, 4):
-            raise _lib.NerfAmdError("start_pose must be [4, 4], got %s" % (tuple(self.start_pose.shape),))
+        self._check_start_pose()
         self.sampler = sampler
         if sampler is not None:
             if not isinstance(sampler, PixelSampler) or sampler.pixels.device != dev:
@@ -735,6 +893,10 @@ class CapturedPoseStep:
             sampler.draw_count.copy_(draws_before)                # the warm-up draws do not count
         with torch.no_grad():
             self.pose.copy_(cam_transf(self.start_pose))          # (the capture left the pose of its own last update there)
+
+    def _check_start_pose(self):
+        if tuple(self.start_pose.shape) != (4, 4):
+            raise _lib.NerfAmdError("start_pose must be [4, 4], got %s" % (tuple(self.start_pose.shape),))
 
     def _body(self):
         H, W, K, chunk = self.args
@@ -772,6 +934,109 @@ class CapturedPoseStep:
         self.graph.replay()
         self.optimizer.note_replayed_step()
         return self.loss
+
+
+class CapturedMultiPoseStep(CapturedPoseStep):
+    """CapturedPoseStep for B pose hypotheses in ONE captured step (multi-start pose estimation: photometric refinement has
+    a narrow basin, so the loop is run from several starts and the best is kept):
+
+        [sampler.draw()] -> poses = cam_transfs(start_poses) [B, 4, 4] -> get_rays_at(H, W, K, poses, pixels) [B, n, 3] x 2
+        -> render_from_rays(rays [2, B n, 3], hypothesis-major rows) -> losses = img2mse_each(rgb.view(B, n, 3), target) [B]
+        -> losses.sum().backward() -> optimizer.step()
+
+    To every field kernel the B hypotheses are one batch of B n rays.  The loss is the SUM over hypotheses, so hypothesis b's
+    gradient is exactly what it would get alone, and Adam is elementwise, so one optim.Adam over the three [B, ...] tensors
+    of a utils.CameraTransfBatch is B independent Adams with a common step count and learning rate.  The pixels (and target)
+    are SHARED by all hypotheses: that makes their losses comparable and lets one sampler.draw() feed all of them.
+
+    Same contracts as CapturedPoseStep (frozen models, optim.Adam over exactly cam_transfs.parameters(), construction leaves
+    parameters, moments, step count and sampler.draw_count as they were, the learning rate is picked up from param_groups,
+    step(pixels, target) or step() with a sampler).  start_poses is [B, 4, 4], or one [4, 4] for all (then the hypotheses
+    differ by the module rows the caller sets).  step() returns `step.losses` [B]; `step.poses` [B, 4, 4] are the poses AFTER
+    the update; both are device tensors that the next replay overwrites.  The whole body runs on the capturing stream.  With
+    chunk < B n the renderer's chunk loop runs (correct, pointless): pass chunk >= B n.
+
+        cams = utils.CameraTransfBatch(B).to(device)
+        opt = optim.Adam(cams.parameters(), lr=lrate, betas=(0.9, 0.999))
+        step = utils.CapturedMultiPoseStep(renderer, H, W, K, B * n_rays, coarse, fine, cams, start_poses, opt, n_rays, sampler=s)
+        for k in range(n_iters):
+            losses = step()                                      # [B], device
+            for g in opt.param_groups: g['lr'] = lrate * 0.8 ** ((k + 1) / 100)
+        winner = cams.pose_module(int(best))                     # go on alone in a CapturedPoseStep
+    """
+
+    cam_transfs = property(lambda self: self.cam_transf)
+    start_poses = property(lambda self: self.start_pose)
+    losses = property(lambda self: self.loss)
+    poses = property(lambda self: self.pose)
+
+    def _check_start_pose(self):
+        if not isinstance(self.cam_transf, CameraTransfBatch):
+            raise _lib.NerfAmdError("CapturedMultiPoseStep steps a utils.CameraTransfBatch, got %s" % type(self.cam_transf).__name__)
+        B = self.cam_transf.n_poses
+        if tuple(self.start_pose.shape) not in ((4, 4), (B, 4, 4)):
+            raise _lib.NerfAmdError("start_poses must be [%d, 4, 4] (the module's hypotheses) or [4, 4], got %s"
+                                    % (B, tuple(self.start_pose.shape)))
+
+    def _body(self):
+        H, W, K, chunk = self.args
+        coarse, fine = self.models
+        B, n = self.cam_transf.n_poses, self.pixels.shape[0]
+        for p in self.params:
+            p.grad = None
+        if self.sampler is not None:
+            self.sampler.draw()
+        poses = self.cam_transf(self.start_pose)
+        rays_o, rays_d = get_rays_at(H, W, K, poses, self.pixels)
+        rays = torch.stack([rays_o.view(B * n, 3), rays_d.view(B * n, 3)], 0)
+        rgb, disp, acc, extras = self.renderer.render_from_rays(H, W, K, chunk, rays, coarse, fine, retraw=True)
+        losses = img2mse_each(rgb.reshape(B, n, 3), self.target)
+        losses.sum().backward()
+        self.optimizer.step()
+        self.loss = losses.detach()
+        with torch.no_grad():
+            self.pose = self.cam_transf(self.start_pose)
+
+
+def multistart_scores(losses, window=10):
+    """The selection rule of multi-start pose estimation: losses [steps, B] -> (scores [B], best).  scores[b] is the mean of
+    hypothesis b's last min(window, steps) losses (added in fp32, oldest first, then divided) with NaN counted as +inf; best =
+    argmin(scores) (0-dim int64).  Runs where
+    `losses` lives (no readback for a device tensor); a host array is taken as a CPU tensor."""
+    losses = torch.as_tensor(losses)
+    if losses.dim() != 2 or losses.shape[0] < 1 or losses.shape[1] < 1 or int(window) < 1:
+        raise _lib.NerfAmdError("multistart_scores takes losses [steps >= 1, B >= 1] and window >= 1, got %s, %r" % (tuple(losses.shape), window))
+    tail = losses[-min(int(window), losses.shape[0]):].float()
+    tail = torch.where(torch.isnan(tail), torch.full_like(tail, float("inf")), tail)
+    total = tail[0]
+    for row in tail[1:]:                           # a DEFINED order (oldest step first, fp32): the scores can be restated exactly
+        total = total + row
+    scores = total / tail.shape[0]
+    return scores, torch.argmin(scores)
+
+
+def perturbed_start_poses(pose, n, rot_deg, trans, seed=0):
+    """Hypotheses around a prior, for estimate_relative_pose_multistart: [n, 4, 4] float32 (host, numpy).  Entry 0 is `pose`
+    itself; entry i > 0 is D_i @ pose with D_i a rotation by `rot_deg` degrees about a random unit axis (Rodrigues) and a
+    translation of length `trans` in a random direction, both drawn from np.random.default_rng(seed): deterministic."""
+    if isinstance(pose, torch.Tensor):
+        pose = pose.detach().cpu().numpy()
+    pose = np.asarray(pose, dtype=np.float64)
+    if pose.shape != (4, 4) or int(n) < 1:
+        raise _lib.NerfAmdError("perturbed_start_poses takes a [4, 4] pose and n >= 1, got %s, %r" % (pose.shape, n))
+    rng = np.random.default_rng(seed)
+    out = np.empty((int(n), 4, 4), dtype=np.float32)
+    out[0] = pose
+    a = np.deg2rad(float(rot_deg))
+    for i in range(1, int(n)):
+        axis, direction = rng.standard_normal(3), rng.standard_normal(3)
+        axis, direction = axis / np.linalg.norm(axis), direction / np.linalg.norm(direction)
+        Kx = np.array([[0., -axis[2], axis[1]], [axis[2], 0., -axis[0]], [-axis[1], axis[0], 0.]])
+        D = np.eye(4)
+        D[:3, :3] = np.eye(3) + np.sin(a) * Kx + (1. - np.cos(a)) * (Kx @ Kx)
+        D[:3, 3] = float(trans) * direction
+        out[i] = D @ pose
+    return out
 
 
 class PoseEstimate(tuple):
@@ -813,6 +1078,50 @@ def estimate_relative_pose(coarse_model, fine_model, renderer, sensor_image, sta
         for g in optimizer.param_groups:
             g['lr'] = lrate * (0.8 ** ((k + 1) / 100))
     return PoseEstimate(step.pose.clone(), losses, step)
+
+
+class MultiPoseEstimate(PoseEstimate):
+    """(pose, losses) of utils.estimate_relative_pose_multistart with `.poses` [B, 4, 4], `.scores` [B], `.best` (0-dim int64),
+    all on the device, and `.step`, the CapturedMultiPoseStep it ran."""
+
+    def __new__(cls, pose, losses, step, poses, scores, best):
+        self = super().__new__(cls, pose, losses, step)
+        self.poses, self.scores, self.best = poses, scores, best
+        return self
+
+
+def estimate_relative_pose_multistart(coarse_model, fine_model, renderer, sensor_image, start_poses, K, chunk, *, steps=300,
+                                      batch_size=512, lrate=0.01, strategy='interest_region', kernel_size=5, dil_iter=3, points=None,
+                                      seed=0, window=10):
+    """estimate_relative_pose from B start poses [B, 4, 4] at once (utils.perturbed_start_poses makes them around a prior):
+    one sampler, one CameraTransfBatch, one CapturedMultiPoseStep, the demo's learning-rate schedule.  Every hypothesis sees
+    the same pixels at every step, so the per-step losses [steps, B] are comparable: scores[b] is the mean of hypothesis b's
+    last min(window, steps) losses (NaN counts as +inf, multistart_scores) and best = argmin(scores), taken on the device --
+    nothing is read back inside or after the loop.
+
+    Returns (pose, losses) with pose = poses[best] (device [4, 4]) and losses [steps, B] (device); the tuple also carries
+    .poses [B, 4, 4], .scores [B], .best (0-dim device int64) and .step (go on with step.cam_transfs.pose_module(int(best)))."""
+    from . import optim
+    H, W = int(sensor_image.shape[0]), int(sensor_image.shape[1])
+    dev = next(coarse_model.parameters()).device
+    start_poses = torch.as_tensor(start_poses, dtype=torch.float32)
+    if start_poses.dim() != 3 or tuple(start_poses.shape[1:]) != (4, 4):
+        raise _lib.NerfAmdError("start_poses must be [B, 4, 4], got %s" % (tuple(start_poses.shape),))
+    B = start_poses.shape[0]
+    sampler = PixelSampler(sensor_image, batch_size, strategy=strategy, points=points, kernel_size=kernel_size, dil_iter=dil_iter,
+                           seed=seed, device=dev)
+    cam_transfs = CameraTransfBatch(B).to(dev)
+    optimizer = optim.Adam(cam_transfs.parameters(), lr=lrate, betas=(0.9, 0.999))
+    step = CapturedMultiPoseStep(renderer, H, W, K, max(int(chunk), B * int(batch_size)), coarse_model, fine_model, cam_transfs,
+                                 start_poses, optimizer, batch_size, sampler=sampler)
+    losses = torch.zeros(int(steps), B, device=dev, dtype=torch.float32)
+    for k in range(int(steps)):
+        losses[k].copy_(step())
+        for g in optimizer.param_groups:
+            g['lr'] = lrate * (0.8 ** ((k + 1) / 100))
+    scores, best = multistart_scores(losses, window)
+    poses = step.poses.clone()
+    return MultiPoseEstimate(poses.index_select(0, best.reshape(1))[0], losses, step, poses, scores, best)
 
 
 def save_checkpoints(args, coarse_model, fine_model, optimizer, global_step, i):

@@ -21,6 +21,17 @@ Legs a, b and c are fed from eight prepared pixel sets (no selection cost).  Per
 the timed steps).  Prints one JSON line.
 
     python tools/pose_bench.py [--steps 60] [--warmup 5] [--out profiles/pose_step.json]
+
+--multistart runs another leg INSTEAD (run_multistart): B = 1, 2, 4, 8, 16 pose hypotheses in one utils.CapturedMultiPoseStep
+replay against B sequential replays of utils.CapturedPoseStep, GPU and host ms for both and their ratio per row.  Give each
+invocation its own time limit (a hung device must end the run, not the next tool):
+
+    timeout -k 10 900 python tools/pose_bench.py --multistart --out profiles/pose_multistart.json
+
+--multistart-trace B replays one multi-step 40 times and times nothing, for a kernel timeline of the step:
+
+    timeout -k 10 300 rocprofv3 --kernel-trace --output-format csv -d /tmp/tr -- python3 tools/pose_bench.py --multistart-trace 8 --batch 512 --precision bf16
+    python3 tools/step_timeline.py $(find /tmp/tr -name '*kernel_trace.csv') > profiles/pose_multistart_timeline_B8.txt
 """
 import argparse
 import contextlib
@@ -139,7 +150,8 @@ def draw_kernel_us(sampler, draws=100, repeats=3):
     return best
 
 
-def run(dev, batch, precision, steps, warmup):
+def scene(dev, batch, precision):
+    """Frozen models, renderer, intrinsics, the start pose and eight prepared (pixels, target) sets: what every leg runs on."""
     models = []
     for seed in (0, 10):
         m = nerf.NeRF(**ARCH)
@@ -157,6 +169,11 @@ def run(dev, batch, precision, steps, warmup):
     for _ in range(8):                        # the demo draws a new subset every iteration
         idx = rng.choice(H * W, size=batch, replace=False)
         sets.append((torch.from_numpy(np.stack([idx % W, idx // W], -1)).to(dev), torch.rand(batch, 3, device=dev)))
+    return models, r, K, start, sets
+
+
+def run(dev, batch, precision, steps, warmup):
+    models, r, K, start, sets = scene(dev, batch, precision)
 
     def decay(opt, k):
         for g in opt.param_groups:
@@ -250,14 +267,133 @@ def run(dev, batch, precision, steps, warmup):
     return out
 
 
+MULTISTART_B = (1, 2, 4, 8, 16)
+
+
+def window(step, steps):
+    """(host ms, GPU ms) per call of `step` over `steps` calls: wall time of the enqueue, events around the window."""
+    torch.cuda.synchronize()
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    t0 = time.perf_counter()
+    for k in range(steps):
+        step(k)
+    host = (time.perf_counter() - t0) / steps
+    e1.record()
+    torch.cuda.synchronize()
+    return host * 1e3, e0.elapsed_time(e1) / steps
+
+
+def run_multistart(dev, batch, precision, steps, warmup, repeats):
+    """The multi-start leg: per B, one replay of utils.CapturedMultiPoseStep (B hypotheses around the start pose, B * batch
+    rays to every field kernel) against B sequential replays of the existing utils.CapturedPoseStep -- the yardstick, what a
+    caller runs without the multi-step -- in the same process, on the same pixel sets.  Both are warmed up, then timed in
+    `repeats` alternating windows of `steps` steps; the medians are reported with the extremes of the windows."""
+    models, r, K, start, sets = scene(dev, batch, precision)
+
+    def decay(opt, k):
+        for g in opt.param_groups:
+            g["lr"] = LRATE * (0.8 ** ((k + 1) / 100))
+
+    torch.manual_seed(0)
+    cam = utils.CameraTransf().to(dev)
+    opt = optim.Adam(cam.parameters(), lr=LRATE, betas=(0.9, 0.999))
+    single = utils.CapturedPoseStep(r, H, W, K, 32768, models[0], models[1], cam, start, opt, batch)
+    rows = []
+    for B in MULTISTART_B:
+        starts = torch.from_numpy(utils.perturbed_start_poses(start.cpu().numpy(), B, 5.0, 0.1, seed=0)).to(dev)
+        torch.manual_seed(0)
+        cams = utils.CameraTransfBatch(B).to(dev)
+        opt_m = optim.Adam(cams.parameters(), lr=LRATE, betas=(0.9, 0.999))
+        multi = utils.CapturedMultiPoseStep(r, H, W, K, max(32768, B * batch), models[0], models[1], cams, starts, opt_m, batch)
+
+        def step_multi(k):
+            multi(*sets[k % len(sets)])
+            decay(opt_m, k)
+
+        def step_sequential(k):
+            for _ in range(B):                    # B hypotheses, one after another (each its own replay and pixel copy)
+                single(*sets[k % len(sets)])
+            decay(opt, k)
+
+        for k in range(warmup):
+            step_multi(k)
+            step_sequential(k)
+        m, q = [], []
+        for _ in range(repeats):
+            m.append(window(step_multi, steps))
+            q.append(window(step_sequential, steps))
+        med = lambda v: float(np.median(v))          # noqa: E731
+        row = {"precision": precision, "batch": batch, "B": B,
+               "multi_gpu_ms": med([x[1] for x in m]), "multi_host_ms": med([x[0] for x in m]),
+               "sequential_gpu_ms": med([x[1] for x in q]), "sequential_host_ms": med([x[0] for x in q]),
+               "multi_gpu_ms_min_max": [min(x[1] for x in m), max(x[1] for x in m)],
+               "sequential_gpu_ms_min_max": [min(x[1] for x in q), max(x[1] for x in q)],
+               "losses_finite": bool(torch.isfinite(multi.losses).all())}
+        row["sequential_over_multi_gpu"] = row["sequential_gpu_ms"] / row["multi_gpu_ms"]
+        row["sequential_over_multi_host"] = row["sequential_host_ms"] / row["multi_host_ms"]
+        rows.append(row)
+        print("multistart %s batch %d B %2d: multi %.3f ms GPU (%.3f host), %d sequential %.3f ms GPU (%.3f host), ratio %.2f"
+              % (precision, batch, B, row["multi_gpu_ms"], row["multi_host_ms"], B, row["sequential_gpu_ms"], row["sequential_host_ms"],
+                 row["sequential_over_multi_gpu"]), file=sys.stderr, flush=True)
+        del multi, cams, opt_m
+    return rows
+
+
+def trace_multistart(args):
+    """--multistart-trace B: nothing is timed; 40 replays of one CapturedMultiPoseStep (first --batch, first --precision) for a
+    profiler to look at (tools/step_timeline.py prints the kernels of the last two steps)."""
+    dev = torch.device("cuda:0")
+    B, batch = args.multistart_trace, args.batch[0]
+    models, r, K, start, sets = scene(dev, batch, args.precision[0])
+    starts = torch.from_numpy(utils.perturbed_start_poses(start.cpu().numpy(), B, 5.0, 0.1, seed=0)).to(dev)
+    torch.manual_seed(0)
+    cams = utils.CameraTransfBatch(B).to(dev)
+    opt = optim.Adam(cams.parameters(), lr=LRATE, betas=(0.9, 0.999))
+    multi = utils.CapturedMultiPoseStep(r, H, W, K, max(32768, B * batch), models[0], models[1], cams, starts, opt, batch)
+    for k in range(40):
+        multi(*sets[k % len(sets)])
+    torch.cuda.synchronize()
+    print(json.dumps({"tool": "pose_bench --multistart-trace", "B": B, "batch": batch, "precision": args.precision[0],
+                      "losses": [float(v) for v in multi.losses.cpu()]}))
+
+
+def main_multistart(args):
+    dev = torch.device("cuda:0")
+    steps = max(args.steps, 100)
+    result = {"tool": "pose_bench --multistart", "image": [H, W], "samples": [64, 128], "steps_per_window": steps, "windows": args.repeats,
+              "warmup": args.warmup, "device": torch.cuda.get_device_name(0), "hypotheses": list(MULTISTART_B),
+              "sequential": "ONE utils.CapturedPoseStep object (one module, one start pose) replayed B times per step, each replay with "
+                            "its own copy of the pixel set: the time of B single-hypothesis steps, not B distinct hypotheses",
+              "multi": "one replay of utils.CapturedMultiPoseStep (B distinct hypotheses around the start pose)", "rows": []}
+    for precision in args.precision:
+        for batch in args.batch:
+            result["rows"] += run_multistart(dev, batch, precision, steps, args.warmup, args.repeats)
+    line = json.dumps(result)
+    print(line)
+    if args.out:
+        with open(args.out, "w") as f:
+            f.write(line + "\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--multistart", action="store_true",
+                    help="run the multi-start leg alone: CapturedMultiPoseStep for B in 1..16 against B sequential CapturedPoseStep "
+                         "replays (profiles/pose_multistart.json)")
+    ap.add_argument("--multistart-trace", type=int, default=0, metavar="B",
+                    help="replay one CapturedMultiPoseStep of B hypotheses 40 times and time nothing (run it under a profiler)")
+    ap.add_argument("--repeats", type=int, default=5, help="--multistart: alternating timed windows per row")
     ap.add_argument("--steps", type=int, default=60, help="timed steps per leg (>= 50)")
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--batch", type=int, nargs="+", default=[256, 512])          # the demo's --batch_size default is 512
     ap.add_argument("--precision", nargs="+", default=["bf16", "fp32_split"])
     ap.add_argument("--out", default=None, help="also write the JSON line to this file")
     args = ap.parse_args()
+    if args.multistart_trace:
+        return trace_multistart(args)
+    if args.multistart:
+        return main_multistart(args)
     dev = torch.device("cuda:0")
     result = {"tool": "pose_bench", "image": [H, W], "samples": [64, 128], "steps": args.steps, "warmup": args.warmup,
               "device": torch.cuda.get_device_name(0), "runs": []}
