@@ -420,9 +420,11 @@ int nerf_amd_se3_transform_backward(const float *w, const float *v, const float 
                                     float *g_w, float *g_v, float *g_theta, void *stream);
 
 /* Multi-start pose estimation: B pose hypotheses (1 <= B <= 1024, anything else is NERF_AMD_EINVAL) in one launch each.
- * Every entry point below does for hypothesis b THE SAME OPERATIONS IN THE SAME ORDER as its single-pose twin above (the
- * kernels share their device bodies), so slice b of its result equals a call of the twin on slice b bit for bit.  All
- * buffers fp32 DEVICE; no synchronisation, no allocation, no float atomics; capturable.
+ * Each single-pose entry point above, and nerf_amd_img2mse(_backward) below, IS its batch form here at B = 1: one kernel
+ * and one launcher per operation, hypothesis b = row b of the grid.  So slice b of a batch result equals a call of the
+ * single form on slice b bit for bit.  What the single forms have beyond B = 1 of the batch forms: a `partials` buffer
+ * (the two reductions may then take more than one block, any n) and nerf_amd_img2mse_backward's gy.  All buffers fp32
+ * DEVICE; no synchronisation, no allocation, no float atomics; capturable.
  *
  * se(3): w [B,3], v [B,3], theta [B], T [B,16]; x at x + b * x_stride floats, x_stride = 0 (one x [16] shared by all
  * hypotheses) or 16 (x [B,16]).  One lane per hypothesis, fp64.  _backward: g_T [B,16] -> g_w [B,3], g_v [B,3], g_theta [B]. */
@@ -434,16 +436,16 @@ int nerf_amd_se3_transform_batch_backward(const float *w, const float *v, const 
  * at c2w + b * c2w_pose_stride floats (>= 0), its row r a further r * c2w_row_stride floats on; rays_o / rays_d [B,n,3],
  * one thread per (b, pixel).
  * _backward: g_rays_o / g_rays_d [B,n,3] (either may be NULL = zero) -> g_c2w [B,12] (overwritten), ONE 1024-thread block
- * per hypothesis running the loop, butterfly and wave-order sum of nerf_amd_rays_at_pixels_backward's one-launch path, so
- * n <= 16384 (beyond it NERF_AMD_EINVAL: there is no partials path); n == 0 zeroes g_c2w. */
+ * per hypothesis: nerf_amd_rays_at_pixels_backward's one-launch path (loop, butterfly, wave-order sum), so n <= 16384
+ * (beyond it NERF_AMD_EINVAL, also at B = 1: this entry point has no partials); n == 0 zeroes g_c2w. */
 int nerf_amd_rays_at_pixels_batch(int32_t H, int32_t W, const double *K4 /* HOST */, const float *c2w, int64_t c2w_pose_stride,
                                   int32_t c2w_row_stride, int32_t B, const int32_t *pix, int64_t n, float *rays_o,
                                   float *rays_d, void *stream);
 int nerf_amd_rays_at_pixels_batch_backward(int32_t H, int32_t W, const double *K4, const int32_t *pix, int64_t n, int32_t B,
                                            const float *g_rays_o, const float *g_rays_d, float *g_c2w, void *stream);
 /* One loss per hypothesis: out[b] = mean((x[b] - y_b)^2), x [B,m]; y_b at y + b * y_stride floats, y_stride = 0 (one y [m]
- * shared) or m (y [B,m]).  One block per hypothesis running nerf_amd_img2mse's one-launch path, so 1 <= m <= 16384
- * (beyond it NERF_AMD_EINVAL).  _backward: gx[b,i] = g[b] * 2 (x[b,i] - y_b[i]) / m, g [B] DEVICE, gx [B,m]. */
+ * shared) or m (y [B,m]).  One block per hypothesis: nerf_amd_img2mse's one-launch path, so 1 <= m <= 16384
+ * (beyond it NERF_AMD_EINVAL, also at B = 1).  _backward: gx[b,i] = g[b] * 2 (x[b,i] - y_b[i]) / m, g [B] DEVICE, gx [B,m]. */
 int nerf_amd_img2mse_each(const float *x, const float *y, int64_t y_stride, int64_t m, int32_t B, float *out, void *stream);
 int nerf_amd_img2mse_each_backward(const float *x, const float *y, int64_t y_stride, int64_t m, int32_t B, const float *g,
                                    float *gx, void *stream);

@@ -1145,18 +1145,6 @@ int nerf_amd_get_rays_backward(int32_t H, int32_t W, const double *K4, int64_t p
     return rc ? fail(rc, "get_rays backward launch failed") : NERF_AMD_OK;
 }
 
-int nerf_amd_img2mse(const float *x, const float *y, int64_t n, float *out, float *partials, void *stream) {
-    if (n < 1 || !x || !y || !out) return fail(NERF_AMD_EINVAL, "bad img2mse arguments");
-    int rc = na::launch_img2mse(x, y, n, out, partials, static_cast<hipStream_t>(stream));
-    return rc ? fail(rc, rc == NERF_AMD_EINVAL ? "img2mse: n > 16384 needs the partials buffer" : "img2mse launch failed") : NERF_AMD_OK;
-}
-
-int nerf_amd_img2mse_backward(const float *x, const float *y, int64_t n, const float *g, float *gx, float *gy, void *stream) {
-    if (n < 1 || !x || !y || !g) return fail(NERF_AMD_EINVAL, "bad img2mse_backward arguments");
-    int rc = na::launch_img2mse_bwd(x, y, n, g, gx, gy, static_cast<hipStream_t>(stream));
-    return rc ? fail(rc, "img2mse_backward launch failed") : NERF_AMD_OK;
-}
-
 int nerf_amd_assemble_rays(const float *rays_o, const float *rays_d, const float *viewdir_src, int64_t n, float near,
                            float far, float *out, void *stream) {
     if (n < 0 || (n > 0 && (!rays_o || !rays_d || !out))) return fail(NERF_AMD_EINVAL, "bad assemble_rays arguments");
@@ -1202,91 +1190,112 @@ int nerf_amd_to8b(const float *x, int64_t n, uint8_t *out, void *stream) {
     return rc ? fail(rc, "to8b launch failed") : NERF_AMD_OK;
 }
 
-int nerf_amd_rays_at_pixels(int32_t H, int32_t W, const double *K4, const float *c2w, int32_t c2w_row_stride, const int32_t *pix,
-                            int64_t n, float *rays_o, float *rays_d, void *stream) {
-    if (H < 1 || W < 1 || !K4 || !c2w || c2w_row_stride < 4 || n < 0 || (n > 0 && (!pix || !rays_o || !rays_d)))
-        return fail(NERF_AMD_EINVAL, "bad rays_at_pixels arguments");
-    int rc = launch_rays_at_pixels(K4, c2w, c2w_row_stride, pix, n, rays_o, rays_d, static_cast<hipStream_t>(stream));
-    return rc ? fail(rc, "rays_at_pixels launch failed") : NERF_AMD_OK;
-}
-
-int nerf_amd_rays_at_pixels_backward(int32_t H, int32_t W, const double *K4, const int32_t *pix, int64_t n, const float *g_rays_o,
-                                     const float *g_rays_d, float *g_c2w, float *partials, void *stream) {
-    if (H < 1 || W < 1 || !K4 || n < 0 || (n > 0 && !pix) || !g_c2w) return fail(NERF_AMD_EINVAL, "bad rays_at_pixels_backward arguments");
-    int rc = launch_rays_at_pixels_bwd(K4, pix, n, g_rays_o, g_rays_d, g_c2w, partials, static_cast<hipStream_t>(stream));
-    return rc ? fail(rc, rc == NERF_AMD_EINVAL ? "rays_at_pixels_backward: n > 16384 needs the partials buffer (256 * 12 floats)"
-                                               : "rays_at_pixels_backward launch failed") : NERF_AMD_OK;
-}
-
-int nerf_amd_se3_transform(const float *w, const float *v, const float *theta, const float *x, float *T, void *stream) {
-    if (!w || !v || !theta || !x || !T) return fail(NERF_AMD_EINVAL, "bad se3_transform arguments");
-    int rc = launch_se3_transform(w, v, theta, x, T, static_cast<hipStream_t>(stream));
-    return rc ? fail(rc, "se3_transform launch failed") : NERF_AMD_OK;
-}
-
-int nerf_amd_se3_transform_backward(const float *w, const float *v, const float *theta, const float *x, const float *g_T, float *g_w,
-                                    float *g_v, float *g_theta, void *stream) {
-    if (!w || !v || !theta || !x || !g_T || !g_w || !g_v || !g_theta) return fail(NERF_AMD_EINVAL, "bad se3_transform_backward arguments");
-    int rc = launch_se3_transform_bwd(w, v, theta, x, g_T, g_w, g_v, g_theta, static_cast<hipStream_t>(stream));
-    return rc ? fail(rc, "se3_transform_backward launch failed") : NERF_AMD_OK;
-}
-
-// ---- multi-start pose estimation: B hypotheses per launch -----------------------------------------------------------
+// ---- pose estimation and the loss: se(3), rays at pixels, img2mse, each for B hypotheses per launch ------------------
+// Every single-pose entry point is its batch twin at B = 1.  The checks that all of them repeat are written once here;
+// `name` is the entry point without its prefix, as the messages spell it.
 static bool pose_batch_ok(int32_t B) { return B >= 1 && B <= POSE_BATCH_MAX; }
+static bool se3_ok(const float *w, const float *v, const float *theta, const float *x, int32_t x_stride) {
+    return w && v && theta && x && (x_stride == 0 || x_stride == 16);
+}
+static bool rays_ok(int32_t H, int32_t W, const double *K4, const int32_t *pix, int64_t n) {
+    return H >= 1 && W >= 1 && K4 && n >= 0 && (n == 0 || pix);
+}
+static bool mse_ok(const float *x, const float *y, int64_t y_stride, int64_t m) { return m >= 1 && x && y && (y_stride == 0 || y_stride == m); }
+
+static int pose_refusal(const char *name, bool args_ok, int32_t B) {
+    if (!args_ok) return fail(NERF_AMD_EINVAL, std::string("bad ") + name + " arguments");
+    if (!pose_batch_ok(B)) return fail(NERF_AMD_EINVAL, std::string(name) + ": need 1 <= B <= 1024");
+    return NERF_AMD_OK;
+}
+// The launcher's code as the entry point's: `einval` says what the launcher's one refusal (a reduction of more than one
+// block without `partials`, kernels.h) means for this entry point.
+static int pose_result(const char *name, int rc, const char *einval = nullptr) {
+    if (rc == NERF_AMD_OK) return rc;
+    return fail(rc, rc == NERF_AMD_EINVAL && einval ? std::string(name) + ": " + einval : std::string(name) + " launch failed");
+}
+static const char *const ONE_BLOCK_N = "one block per hypothesis, n <= 16384", *const ONE_BLOCK_M = "one block per hypothesis, m <= 16384";
 
 int nerf_amd_se3_transform_batch(const float *w, const float *v, const float *theta, const float *x, int32_t x_stride, int32_t B,
                                  float *T, void *stream) {
-    if (!w || !v || !theta || !x || !T || (x_stride != 0 && x_stride != 16)) return fail(NERF_AMD_EINVAL, "bad se3_transform_batch arguments");
-    if (!pose_batch_ok(B)) return fail(NERF_AMD_EINVAL, "se3_transform_batch: need 1 <= B <= 1024");
-    int rc = launch_se3_transform_batch(w, v, theta, x, x_stride, B, T, static_cast<hipStream_t>(stream));
-    return rc ? fail(rc, "se3_transform_batch launch failed") : NERF_AMD_OK;
+    if (int rc = pose_refusal("se3_transform_batch", se3_ok(w, v, theta, x, x_stride) && T, B)) return rc;
+    return pose_result("se3_transform_batch", launch_se3_transform(w, v, theta, x, x_stride, B, T, static_cast<hipStream_t>(stream)));
+}
+
+int nerf_amd_se3_transform(const float *w, const float *v, const float *theta, const float *x, float *T, void *stream) {
+    if (int rc = pose_refusal("se3_transform", se3_ok(w, v, theta, x, 0) && T, 1)) return rc;
+    return pose_result("se3_transform", launch_se3_transform(w, v, theta, x, 0, 1, T, static_cast<hipStream_t>(stream)));
 }
 
 int nerf_amd_se3_transform_batch_backward(const float *w, const float *v, const float *theta, const float *x, int32_t x_stride,
                                           int32_t B, const float *g_T, float *g_w, float *g_v, float *g_theta, void *stream) {
-    if (!w || !v || !theta || !x || !g_T || !g_w || !g_v || !g_theta || (x_stride != 0 && x_stride != 16))
-        return fail(NERF_AMD_EINVAL, "bad se3_transform_batch_backward arguments");
-    if (!pose_batch_ok(B)) return fail(NERF_AMD_EINVAL, "se3_transform_batch_backward: need 1 <= B <= 1024");
-    int rc = launch_se3_transform_batch_bwd(w, v, theta, x, x_stride, B, g_T, g_w, g_v, g_theta, static_cast<hipStream_t>(stream));
-    return rc ? fail(rc, "se3_transform_batch_backward launch failed") : NERF_AMD_OK;
+    if (int rc = pose_refusal("se3_transform_batch_backward", se3_ok(w, v, theta, x, x_stride) && g_T && g_w && g_v && g_theta, B)) return rc;
+    return pose_result("se3_transform_batch_backward",
+                       launch_se3_transform_bwd(w, v, theta, x, x_stride, B, g_T, g_w, g_v, g_theta, static_cast<hipStream_t>(stream)));
+}
+
+int nerf_amd_se3_transform_backward(const float *w, const float *v, const float *theta, const float *x, const float *g_T, float *g_w,
+                                    float *g_v, float *g_theta, void *stream) {
+    if (int rc = pose_refusal("se3_transform_backward", se3_ok(w, v, theta, x, 0) && g_T && g_w && g_v && g_theta, 1)) return rc;
+    return pose_result("se3_transform_backward",
+                       launch_se3_transform_bwd(w, v, theta, x, 0, 1, g_T, g_w, g_v, g_theta, static_cast<hipStream_t>(stream)));
 }
 
 int nerf_amd_rays_at_pixels_batch(int32_t H, int32_t W, const double *K4, const float *c2w, int64_t c2w_pose_stride,
                                   int32_t c2w_row_stride, int32_t B, const int32_t *pix, int64_t n, float *rays_o, float *rays_d,
                                   void *stream) {
-    if (H < 1 || W < 1 || !K4 || !c2w || c2w_pose_stride < 0 || c2w_row_stride < 4 || n < 0 || (n > 0 && (!pix || !rays_o || !rays_d)))
-        return fail(NERF_AMD_EINVAL, "bad rays_at_pixels_batch arguments");
-    if (!pose_batch_ok(B)) return fail(NERF_AMD_EINVAL, "rays_at_pixels_batch: need 1 <= B <= 1024");
-    int rc = launch_rays_at_pixels_batch(K4, c2w, c2w_pose_stride, c2w_row_stride, B, pix, n, rays_o, rays_d,
-                                         static_cast<hipStream_t>(stream));
-    return rc ? fail(rc, "rays_at_pixels_batch launch failed") : NERF_AMD_OK;
+    const bool ok = rays_ok(H, W, K4, pix, n) && c2w && c2w_pose_stride >= 0 && c2w_row_stride >= 4 && (n == 0 || (rays_o && rays_d));
+    if (int rc = pose_refusal("rays_at_pixels_batch", ok, B)) return rc;
+    return pose_result("rays_at_pixels_batch", launch_rays_at_pixels(K4, c2w, c2w_pose_stride, c2w_row_stride, B, pix, n, rays_o, rays_d,
+                                                                     static_cast<hipStream_t>(stream)));
+}
+
+int nerf_amd_rays_at_pixels(int32_t H, int32_t W, const double *K4, const float *c2w, int32_t c2w_row_stride, const int32_t *pix,
+                            int64_t n, float *rays_o, float *rays_d, void *stream) {
+    const bool ok = rays_ok(H, W, K4, pix, n) && c2w && c2w_row_stride >= 4 && (n == 0 || (rays_o && rays_d));
+    if (int rc = pose_refusal("rays_at_pixels", ok, 1)) return rc;
+    return pose_result("rays_at_pixels",
+                       launch_rays_at_pixels(K4, c2w, 0, c2w_row_stride, 1, pix, n, rays_o, rays_d, static_cast<hipStream_t>(stream)));
 }
 
 int nerf_amd_rays_at_pixels_batch_backward(int32_t H, int32_t W, const double *K4, const int32_t *pix, int64_t n, int32_t B,
                                            const float *g_rays_o, const float *g_rays_d, float *g_c2w, void *stream) {
-    if (H < 1 || W < 1 || !K4 || n < 0 || (n > 0 && !pix) || !g_c2w) return fail(NERF_AMD_EINVAL, "bad rays_at_pixels_batch_backward arguments");
-    if (!pose_batch_ok(B)) return fail(NERF_AMD_EINVAL, "rays_at_pixels_batch_backward: need 1 <= B <= 1024");
-    if (n > RAYS_AT_BWD_PER_BLOCK)
-        return fail(NERF_AMD_EINVAL, "rays_at_pixels_batch_backward: one block per hypothesis, n <= 16384");
-    int rc = launch_rays_at_pixels_batch_bwd(K4, pix, n, B, g_rays_o, g_rays_d, g_c2w, static_cast<hipStream_t>(stream));
-    return rc ? fail(rc, "rays_at_pixels_batch_backward launch failed") : NERF_AMD_OK;
+    if (int rc = pose_refusal("rays_at_pixels_batch_backward", rays_ok(H, W, K4, pix, n) && g_c2w, B)) return rc;
+    return pose_result("rays_at_pixels_batch_backward",
+                       launch_rays_at_pixels_bwd(K4, pix, n, B, g_rays_o, g_rays_d, g_c2w, nullptr, static_cast<hipStream_t>(stream)),
+                       ONE_BLOCK_N);
+}
+
+int nerf_amd_rays_at_pixels_backward(int32_t H, int32_t W, const double *K4, const int32_t *pix, int64_t n, const float *g_rays_o,
+                                     const float *g_rays_d, float *g_c2w, float *partials, void *stream) {
+    if (int rc = pose_refusal("rays_at_pixels_backward", rays_ok(H, W, K4, pix, n) && g_c2w, 1)) return rc;
+    return pose_result("rays_at_pixels_backward",
+                       launch_rays_at_pixels_bwd(K4, pix, n, 1, g_rays_o, g_rays_d, g_c2w, partials, static_cast<hipStream_t>(stream)),
+                       "n > 16384 needs the partials buffer (256 * 12 floats)");
 }
 
 int nerf_amd_img2mse_each(const float *x, const float *y, int64_t y_stride, int64_t m, int32_t B, float *out, void *stream) {
-    if (m < 1 || !x || !y || !out || (y_stride != 0 && y_stride != m)) return fail(NERF_AMD_EINVAL, "bad img2mse_each arguments");
-    if (!pose_batch_ok(B)) return fail(NERF_AMD_EINVAL, "img2mse_each: need 1 <= B <= 1024");
-    if (m > IMG2MSE_EACH_MAX) return fail(NERF_AMD_EINVAL, "img2mse_each: one block per hypothesis, m <= 16384");
-    int rc = launch_img2mse_each(x, y, y_stride, m, B, out, static_cast<hipStream_t>(stream));
-    return rc ? fail(rc, "img2mse_each launch failed") : NERF_AMD_OK;
+    if (int rc = pose_refusal("img2mse_each", mse_ok(x, y, y_stride, m) && out, B)) return rc;
+    return pose_result("img2mse_each", na::launch_img2mse(x, y, y_stride, m, B, out, nullptr, static_cast<hipStream_t>(stream)), ONE_BLOCK_M);
+}
+
+int nerf_amd_img2mse(const float *x, const float *y, int64_t n, float *out, float *partials, void *stream) {
+    if (int rc = pose_refusal("img2mse", mse_ok(x, y, n, n) && out, 1)) return rc;
+    return pose_result("img2mse", na::launch_img2mse(x, y, n, n, 1, out, partials, static_cast<hipStream_t>(stream)),
+                       "n > 16384 needs the partials buffer");
 }
 
 int nerf_amd_img2mse_each_backward(const float *x, const float *y, int64_t y_stride, int64_t m, int32_t B, const float *g, float *gx,
                                    void *stream) {
-    if (m < 1 || !x || !y || !g || !gx || (y_stride != 0 && y_stride != m)) return fail(NERF_AMD_EINVAL, "bad img2mse_each_backward arguments");
-    if (!pose_batch_ok(B)) return fail(NERF_AMD_EINVAL, "img2mse_each_backward: need 1 <= B <= 1024");
-    if (m > IMG2MSE_EACH_MAX) return fail(NERF_AMD_EINVAL, "img2mse_each_backward: one block per hypothesis, m <= 16384");
-    int rc = launch_img2mse_each_bwd(x, y, y_stride, m, B, g, gx, static_cast<hipStream_t>(stream));
-    return rc ? fail(rc, "img2mse_each_backward launch failed") : NERF_AMD_OK;
+    if (int rc = pose_refusal("img2mse_each_backward", mse_ok(x, y, y_stride, m) && g && gx, B)) return rc;
+    // no reduction, so nothing in the launcher limits m: the documented limit of the pair is kept here
+    if (m > IMG2MSE_EACH_MAX) return fail(NERF_AMD_EINVAL, std::string("img2mse_each_backward: ") + ONE_BLOCK_M);
+    return pose_result("img2mse_each_backward",
+                       na::launch_img2mse_bwd(x, y, y_stride, m, B, g, gx, nullptr, static_cast<hipStream_t>(stream)));
+}
+
+int nerf_amd_img2mse_backward(const float *x, const float *y, int64_t n, const float *g, float *gx, float *gy, void *stream) {
+    if (int rc = pose_refusal("img2mse_backward", mse_ok(x, y, n, n) && g, 1)) return rc;
+    return pose_result("img2mse_backward", na::launch_img2mse_bwd(x, y, n, n, 1, g, gx, gy, static_cast<hipStream_t>(stream)));
 }
 
 int nerf_amd_draw_pixels(int64_t M, int32_t n, uint32_t seed, int64_t *draw_count, const int32_t *region, int32_t H, int32_t W,

@@ -140,8 +140,6 @@ int lane_acquire(int device, int n_events, hipStream_t *side, std::vector<hipEve
 void lane_release(int device, const std::vector<hipEvent_t> &events);
 int lane_streams(int device, int n, hipStream_t *out);      // the device's side stream and up to two more
 
-int launch_img2mse(const float *x, const float *y, int64_t n, float *out, float *partials, hipStream_t s);
-int launch_img2mse_bwd(const float *x, const float *y, int64_t n, const float *g, float *gx, float *gy, hipStream_t s);
 int launch_assemble_rays(const float *o, const float *d, const float *v, int64_t n, float near, float far, float *out, hipStream_t s);
 
 // adam.hip
@@ -193,29 +191,24 @@ int launch_to8b(const float *x, int64_t n, uint8_t *out, hipStream_t s);
 int launch_make_rays(int H, int W, const double *K4, const float *c2w, const float *c2w_static,
                      int64_t pix0, int64_t n, float near, float far, int use_viewdirs, int ndc,
                      float *rays_out, hipStream_t s);
-// pose estimation (demo_est_rel_pose.py:74-98): rays at selected pixels with the pose in device memory, and the se(3) module
+// pose estimation (demo_est_rel_pose.py:74-98): rays at selected pixels with the pose in device memory, the se(3) module and
+// the loss, each for B hypotheses per launch (multi-start pose estimation); one pose, and utils.img2mse, are B = 1.  Slice b
+// of a batch is bit-equal to the B = 1 launch on hypothesis b.  The two reductions (img2mse, rays_at_pixels_bwd) take one
+// block per 16384 values: more than one block needs `partials` (256 floats, 256 * 12 floats) and B = 1, EINVAL otherwise --
+// hence the one-block limits of the batch entry points, which pass no partials.
 constexpr int RAYS_AT_BWD_PER_BLOCK = 16384, RAYS_AT_BWD_MAX_BLOCKS = 256;
-int launch_rays_at_pixels(const double *K4, const float *c2w, int c2w_stride, const int32_t *pix, int64_t n, float *rays_o,
-                          float *rays_d, hipStream_t s);
-int launch_rays_at_pixels_bwd(const double *K4, const int32_t *pix, int64_t n, const float *g_o, const float *g_d, float *g_c2w,
-                              float *partials, hipStream_t s);
-int launch_se3_transform(const float *w, const float *v, const float *theta, const float *x, float *T, hipStream_t s);
-int launch_se3_transform_bwd(const float *w, const float *v, const float *theta, const float *x, const float *g_T, float *g_w,
-                             float *g_v, float *g_theta, hipStream_t s);
-// multi-start pose estimation: B hypotheses per launch, each slice bit-equal to the single-pose launcher above (shared
-// device bodies).  One block per hypothesis in the two reductions, hence their one-launch limits (EINVAL beyond).
 constexpr int POSE_BATCH_MAX = 1024, IMG2MSE_EACH_MAX = 16384;
-int launch_se3_transform_batch(const float *w, const float *v, const float *theta, const float *x, int x_stride, int B, float *T,
-                               hipStream_t s);
-int launch_se3_transform_batch_bwd(const float *w, const float *v, const float *theta, const float *x, int x_stride, int B,
-                                   const float *g_T, float *g_w, float *g_v, float *g_theta, hipStream_t s);
-int launch_rays_at_pixels_batch(const double *K4, const float *c2w, int64_t c2w_pose_stride, int c2w_row_stride, int B,
-                                const int32_t *pix, int64_t n, float *rays_o, float *rays_d, hipStream_t s);
-int launch_rays_at_pixels_batch_bwd(const double *K4, const int32_t *pix, int64_t n, int B, const float *g_o, const float *g_d,
-                                    float *g_c2w, hipStream_t s);
-int launch_img2mse_each(const float *x, const float *y, int64_t y_stride, int64_t m, int B, float *out, hipStream_t s);
-int launch_img2mse_each_bwd(const float *x, const float *y, int64_t y_stride, int64_t m, int B, const float *g, float *gx,
-                            hipStream_t s);
+int launch_se3_transform(const float *w, const float *v, const float *theta, const float *x, int x_stride, int B, float *T,
+                         hipStream_t s);
+int launch_se3_transform_bwd(const float *w, const float *v, const float *theta, const float *x, int x_stride, int B, const float *g_T,
+                             float *g_w, float *g_v, float *g_theta, hipStream_t s);
+int launch_rays_at_pixels(const double *K4, const float *c2w, int64_t c2w_pose_stride, int c2w_row_stride, int B, const int32_t *pix,
+                          int64_t n, float *rays_o, float *rays_d, hipStream_t s);
+int launch_rays_at_pixels_bwd(const double *K4, const int32_t *pix, int64_t n, int B, const float *g_o, const float *g_d, float *g_c2w,
+                              float *partials, hipStream_t s);
+int launch_img2mse(const float *x, const float *y, int64_t y_stride, int64_t n, int B, float *out, float *partials, hipStream_t s);
+int launch_img2mse_bwd(const float *x, const float *y, int64_t y_stride, int64_t n, int B, const float *g, float *gx, float *gy,
+                       hipStream_t s);
 // pixel selection for pose estimation (pixel_select.hip; demo_est_rel_pose.py:35-47, :75-79)
 int launch_draw_pixels(int64_t M, int n, uint32_t seed, int64_t *draw_count, const int32_t *region, int W, const float *image,
                        int64_t row_stride, int C, int32_t *pixels, float *target, hipStream_t s);

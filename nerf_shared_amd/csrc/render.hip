@@ -783,6 +783,20 @@ int launch_to8b(const float *x, int64_t n, uint8_t *out, hipStream_t s) {
 // ---- utils.img2mse (utils.py:24): mean((x - y)^2) and its gradient, one launch each --------------------------------
 constexpr int MSE_BLOCK = 1024, MSE_PER_BLOCK = 16384, MSE_MAX_BLOCKS = 256;
 
+// Blocks of a fixed-order reduction over n values (img2mse, the pose gradient of rays_at_pixels): one per `per_block` values,
+// at least one, at most `max_blocks` (the rows of `partials`; the loops are grid-strided, so any grid covers any n).
+// THE rule of both launchers: more than one block needs `partials`, and that path is single-pose only (B > 1 with more than
+// one block is EINVAL, nothing launched) -- so without `partials` a launcher is limited to one block = 16384 values.
+constexpr int reduce_blocks(int64_t n, int per_block, int max_blocks) {
+    const int64_t blocks = (n + per_block - 1) / per_block;
+    return blocks < 1 ? 1 : blocks > max_blocks ? max_blocks : (int)blocks;
+}
+static_assert(reduce_blocks(1, 16384, 256) == 1 && reduce_blocks(16384, 16384, 256) == 1 && reduce_blocks(16385, 16384, 256) == 2,
+              "one block up to 16384 values, two from 16385");
+static_assert(reduce_blocks(256 * 16384, 16384, 256) == 256 && reduce_blocks(256 * 16384 + 1, 16384, 256) == 256 &&
+              reduce_blocks((int64_t)1 << 40, 16384, 256) == 256, "clamped at the 256 rows of partials");
+static_assert(IMG2MSE_EACH_MAX == MSE_PER_BLOCK && IMG2MSE_EACH_MAX == RAYS_AT_BWD_PER_BLOCK, "the batch limits are the one-block paths");
+
 __device__ __forceinline__ float block_sum_1024(float v, float *part /* [16] LDS */) {
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
@@ -795,8 +809,7 @@ __device__ __forceinline__ float block_sum_1024(float v, float *part /* [16] LDS
     return t;                        // valid in thread 0
 }
 
-// Block `block` of `n_blocks` of one mean((x - y)^2) over n values: the body of img2mse_kernel and of img2mse_each_kernel (which
-// runs it as block 0 of 1 per hypothesis -- the same loop, butterfly and wave-order sum, so the same bits).
+// Block `block` of `n_blocks` of one mean((x - y)^2) over n values (one block: the loop, butterfly and wave-order sum end in out[0]).
 __device__ __forceinline__ void img2mse_block(const float *x, const float *y, int64_t n, float *out, float *partials, int block,
                                               int n_blocks, float *part /* [16] LDS */) {
     float acc = 0.f;
@@ -812,16 +825,13 @@ __device__ __forceinline__ void img2mse_block(const float *x, const float *y, in
     }
 }
 
-__global__ __launch_bounds__(MSE_BLOCK) void img2mse_kernel(const float *x, const float *y, int64_t n, float *out, float *partials) {
+// grid (blocks, B): row b = blockIdx.y is one loss, out[b] = mean((x[b] - y_b)^2) with x [B, n] and y_b at b * y_stride (0: shared).
+// utils.img2mse is B = 1; several blocks (B = 1 only) leave their sums in `partials` for the finish kernel.
+__global__ __launch_bounds__(MSE_BLOCK) void img2mse_kernel(const float *x, const float *y, int64_t y_stride, int64_t n, float *out,
+                                                            float *partials) {
     __shared__ float part[MSE_BLOCK / 64];
-    img2mse_block(x, y, n, out, partials, (int)blockIdx.x, (int)gridDim.x, part);
-}
-
-// One loss per hypothesis: block b is img2mse_kernel's single-block path on x[b], y_b.
-__global__ __launch_bounds__(MSE_BLOCK) void img2mse_each_kernel(const float *x, const float *y, int64_t y_stride, int64_t m, float *out) {
-    __shared__ float part[MSE_BLOCK / 64];
-    const int64_t b = blockIdx.x;
-    img2mse_block(x + b * m, y + b * y_stride, m, out + b, nullptr, 0, 1, part);
+    const int64_t b = blockIdx.y;
+    img2mse_block(x + b * n, y + b * y_stride, n, out + b, partials, (int)blockIdx.x, (int)gridDim.x, part);
 }
 
 __global__ __launch_bounds__(MSE_MAX_BLOCKS) void img2mse_finish_kernel(const float *partials, int n_parts, int64_t n, float *out) {
@@ -835,7 +845,7 @@ __global__ __launch_bounds__(MSE_MAX_BLOCKS) void img2mse_finish_kernel(const fl
     }
 }
 
-// gx = g[0] * 2 (x - y) / n, gy = -gx over the grid's x dimension: the body of img2mse_bwd_kernel and img2mse_each_bwd_kernel.
+// gx = g[0] * 2 (x - y) / n, gy = -gx over the grid's x dimension.
 __device__ __forceinline__ void img2mse_bwd_body(const float *x, const float *y, int64_t n, const float *g, float *gx, float *gy) {
     const float s = g[0] * (2.0f / (float)n);
     const int64_t stride = (int64_t)gridDim.x * 256;
@@ -846,46 +856,29 @@ __device__ __forceinline__ void img2mse_bwd_body(const float *x, const float *y,
     }
 }
 
-__global__ __launch_bounds__(256) void img2mse_bwd_kernel(const float *x, const float *y, int64_t n, const float *g, float *gx, float *gy) {
-    img2mse_bwd_body(x, y, n, g, gx, gy);
-}
-
-// grid (blocks over m, B): row blockIdx.y is img2mse_bwd_kernel on x[b], y_b with the scalar g[b].
-__global__ __launch_bounds__(256) void img2mse_each_bwd_kernel(const float *x, const float *y, int64_t y_stride, int64_t m, const float *g,
-                                                               float *gx) {
+// grid (blocks over n, B): row b = blockIdx.y is the gradient of loss b with the scalar g[b]; gx, gy [B, n], either may be null.
+__global__ __launch_bounds__(256) void img2mse_bwd_kernel(const float *x, const float *y, int64_t y_stride, int64_t n, const float *g,
+                                                          float *gx, float *gy) {
     const int64_t b = blockIdx.y;
-    img2mse_bwd_body(x + b * m, y + b * y_stride, m, g + b, gx + b * m, nullptr);
+    img2mse_bwd_body(x + b * n, y + b * y_stride, n, g + b, gx ? gx + b * n : nullptr, gy ? gy + b * n : nullptr);
 }
 
-int launch_img2mse(const float *x, const float *y, int64_t n, float *out, float *partials, hipStream_t s) {
-    int64_t blocks = (n + MSE_PER_BLOCK - 1) / MSE_PER_BLOCK;
-    if (blocks < 1) blocks = 1;
-    if (blocks > MSE_MAX_BLOCKS) blocks = MSE_MAX_BLOCKS;
-    if (blocks > 1 && !partials) return NERF_AMD_EINVAL;
-    hipLaunchKernelGGL(img2mse_kernel, dim3((unsigned)blocks), dim3(MSE_BLOCK), 0, s, x, y, n, out, partials);
-    if (blocks > 1) hipLaunchKernelGGL(img2mse_finish_kernel, dim3(1), dim3(MSE_MAX_BLOCKS), 0, s, partials, (int)blocks, n, out);
+int launch_img2mse(const float *x, const float *y, int64_t y_stride, int64_t n, int B, float *out, float *partials, hipStream_t s) {
+    if (B < 1 || B > POSE_BATCH_MAX || n < 1) return NERF_AMD_EINVAL;
+    const int blocks = reduce_blocks(n, MSE_PER_BLOCK, MSE_MAX_BLOCKS);
+    if (blocks > 1 && (!partials || B > 1)) return NERF_AMD_EINVAL;
+    hipLaunchKernelGGL(img2mse_kernel, dim3((unsigned)blocks, (unsigned)B), dim3(MSE_BLOCK), 0, s, x, y, y_stride, n, out, partials);
+    if (blocks > 1) hipLaunchKernelGGL(img2mse_finish_kernel, dim3(1), dim3(MSE_MAX_BLOCKS), 0, s, partials, blocks, n, out);
     return hipGetLastError() == hipSuccess ? NERF_AMD_OK : NERF_AMD_EHIP;
 }
 
-int launch_img2mse_bwd(const float *x, const float *y, int64_t n, const float *g, float *gx, float *gy, hipStream_t s) {
+int launch_img2mse_bwd(const float *x, const float *y, int64_t y_stride, int64_t n, int B, const float *g, float *gx, float *gy,
+                       hipStream_t s) {
+    if (B < 1 || B > POSE_BATCH_MAX) return NERF_AMD_EINVAL;
     if (n <= 0) return NERF_AMD_OK;
     int64_t blocks = (n + 1023) / 1024;
     if (blocks > 2048) blocks = 2048;
-    hipLaunchKernelGGL(img2mse_bwd_kernel, dim3((unsigned)blocks), dim3(256), 0, s, x, y, n, g, gx, gy);
-    return hipGetLastError() == hipSuccess ? NERF_AMD_OK : NERF_AMD_EHIP;
-}
-
-int launch_img2mse_each(const float *x, const float *y, int64_t y_stride, int64_t m, int B, float *out, hipStream_t s) {
-    if (B < 1 || B > POSE_BATCH_MAX || m < 1 || m > IMG2MSE_EACH_MAX) return NERF_AMD_EINVAL;
-    static_assert(IMG2MSE_EACH_MAX == MSE_PER_BLOCK, "img2mse_each is img2mse's one-block path");
-    hipLaunchKernelGGL(img2mse_each_kernel, dim3((unsigned)B), dim3(MSE_BLOCK), 0, s, x, y, y_stride, m, out);
-    return hipGetLastError() == hipSuccess ? NERF_AMD_OK : NERF_AMD_EHIP;
-}
-
-int launch_img2mse_each_bwd(const float *x, const float *y, int64_t y_stride, int64_t m, int B, const float *g, float *gx,
-                            hipStream_t s) {
-    if (B < 1 || B > POSE_BATCH_MAX || m < 1 || m > IMG2MSE_EACH_MAX) return NERF_AMD_EINVAL;
-    hipLaunchKernelGGL(img2mse_each_bwd_kernel, dim3((unsigned)((m + 1023) / 1024), (unsigned)B), dim3(256), 0, s, x, y, y_stride, m, g, gx);
+    hipLaunchKernelGGL(img2mse_bwd_kernel, dim3((unsigned)blocks, (unsigned)B), dim3(256), 0, s, x, y, y_stride, n, g, gx, gy);
     return hipGetLastError() == hipSuccess ? NERF_AMD_OK : NERF_AMD_EHIP;
 }
 
@@ -949,36 +942,22 @@ __device__ __forceinline__ void ray_at_pixel(PixCam k, const float *c2w, int str
     rays_d[3 * idx] = d[0]; rays_d[3 * idx + 1] = d[1]; rays_d[3 * idx + 2] = d[2];
 }
 
-__global__ __launch_bounds__(256) void rays_at_pixels_kernel(PixCam k, const float *c2w, int stride, const int32_t *pix, int64_t n,
-                                                             float *rays_o, float *rays_d) {
-    const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (idx >= n) return;
-    ray_at_pixel(k, c2w, stride, pix, idx, rays_o, rays_d);
-}
-
-// B poses at the same n pixels: grid (blocks over n, B), one thread per (b, pixel); rays_o / rays_d [B, n, 3].
-__global__ __launch_bounds__(256) void rays_at_pixels_batch_kernel(PixCam k, const float *c2w, int64_t pose_stride, int stride,
-                                                                   const int32_t *pix, int64_t n, float *rays_o, float *rays_d) {
+// B poses at the same n pixels: grid (blocks over n, B), one thread per (b, pixel); pose b at c2w + b * pose_stride, rays_o /
+// rays_d [B, n, 3].  One pose is B = 1 (pose_stride 0).
+__global__ __launch_bounds__(256) void rays_at_pixels_kernel(PixCam k, const float *c2w, int64_t pose_stride, int stride,
+                                                             const int32_t *pix, int64_t n, float *rays_o, float *rays_d) {
     const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x, b = blockIdx.y;
     if (idx >= n) return;
     ray_at_pixel(k, c2w + b * pose_stride, stride, pix, idx, rays_o + b * n * 3, rays_d + b * n * 3);
 }
 
-int launch_rays_at_pixels(const double *K4, const float *c2w, int c2w_stride, const int32_t *pix, int64_t n, float *rays_o,
-                          float *rays_d, hipStream_t s) {
-    if (n <= 0) return NERF_AMD_OK;
-    const PixCam k = {(float)K4[0], (float)K4[1], (float)K4[2], (float)K4[3]};
-    hipLaunchKernelGGL(rays_at_pixels_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, k, c2w, c2w_stride, pix, n, rays_o, rays_d);
-    return hipGetLastError() == hipSuccess ? NERF_AMD_OK : NERF_AMD_EHIP;
-}
-
-int launch_rays_at_pixels_batch(const double *K4, const float *c2w, int64_t c2w_pose_stride, int c2w_row_stride, int B,
-                                const int32_t *pix, int64_t n, float *rays_o, float *rays_d, hipStream_t s) {
+int launch_rays_at_pixels(const double *K4, const float *c2w, int64_t c2w_pose_stride, int c2w_row_stride, int B, const int32_t *pix,
+                          int64_t n, float *rays_o, float *rays_d, hipStream_t s) {
     if (B < 1 || B > POSE_BATCH_MAX) return NERF_AMD_EINVAL;
     if (n <= 0) return NERF_AMD_OK;
     const PixCam k = {(float)K4[0], (float)K4[1], (float)K4[2], (float)K4[3]};
-    hipLaunchKernelGGL(rays_at_pixels_batch_kernel, dim3((unsigned)((n + 255) / 256), (unsigned)B), dim3(256), 0, s, k, c2w,
-                       c2w_pose_stride, c2w_row_stride, pix, n, rays_o, rays_d);
+    hipLaunchKernelGGL(rays_at_pixels_kernel, dim3((unsigned)((n + 255) / 256), (unsigned)B), dim3(256), 0, s, k, c2w, c2w_pose_stride,
+                       c2w_row_stride, pix, n, rays_o, rays_d);
     return hipGetLastError() == hipSuccess ? NERF_AMD_OK : NERF_AMD_EHIP;
 }
 
@@ -986,9 +965,9 @@ int launch_rays_at_pixels_batch(const double *K4, const float *c2w, int64_t c2w_
 // adds its rays in index order, a butterfly adds the 64 lanes of a wave (every lane ends with the same bits), thread m < 12
 // adds the 16 wave sums of entry m in wave order; several blocks leave their 12 sums in `partials` for the finish kernel.
 // The loop is grid-strided, so any grid covers any n: RAYS_AT_BWD_PER_BLOCK (kernels.h) only chooses how many blocks are
-// launched (<= RAYS_AT_BWD_MAX_BLOCKS = the rows of `partials`) and need not be a multiple of the block size.
+// launched (reduce_blocks above: <= RAYS_AT_BWD_MAX_BLOCKS = the rows of `partials`) and need not be a multiple of the block size.
 constexpr int RAP_BLOCK = 1024;
-// Block `block` of `n_blocks`: the body of rays_at_pixels_bwd_kernel and of rays_at_pixels_batch_bwd_kernel (block 0 of 1 per hypothesis).
+// Block `block` of `n_blocks` of one pose's gradient.
 __device__ __forceinline__ void rays_at_pixels_bwd_block(PixCam k, const int32_t *pix, int64_t n, const float *g_o, const float *g_d,
                                                          float *g_c2w, float *partials, int block, int n_blocks,
                                                          float (*part)[12] /* [RAP_BLOCK / 64][12] LDS */) {
@@ -1022,19 +1001,14 @@ __device__ __forceinline__ void rays_at_pixels_bwd_block(PixCam k, const int32_t
     }
 }
 
+// grid (blocks, B): row b = blockIdx.y is hypothesis b's gradient over its n rays (g_o / g_d [B, n, 3], g_c2w [B, 12]); several
+// blocks (B = 1 only) leave their 12 sums in `partials` for the finish kernel.
 __global__ __launch_bounds__(RAP_BLOCK) void rays_at_pixels_bwd_kernel(PixCam k, const int32_t *pix, int64_t n, const float *g_o,
                                                                        const float *g_d, float *g_c2w, float *partials) {
     __shared__ float part[RAP_BLOCK / 64][12];
-    rays_at_pixels_bwd_block(k, pix, n, g_o, g_d, g_c2w, partials, (int)blockIdx.x, (int)gridDim.x, part);
-}
-
-// One block per hypothesis: the one-launch path above over hypothesis b's n rays (g_o / g_d [B, n, 3], g_c2w [B, 12]).
-__global__ __launch_bounds__(RAP_BLOCK) void rays_at_pixels_batch_bwd_kernel(PixCam k, const int32_t *pix, int64_t n, const float *g_o,
-                                                                             const float *g_d, float *g_c2w) {
-    __shared__ float part[RAP_BLOCK / 64][12];
-    const int64_t b = blockIdx.x;
-    rays_at_pixels_bwd_block(k, pix, n, g_o ? g_o + b * n * 3 : nullptr, g_d ? g_d + b * n * 3 : nullptr, g_c2w + b * 12, nullptr, 0, 1,
-                             part);
+    const int64_t b = blockIdx.y;
+    rays_at_pixels_bwd_block(k, pix, n, g_o ? g_o + b * n * 3 : nullptr, g_d ? g_d + b * n * 3 : nullptr, g_c2w + b * 12, partials,
+                             (int)blockIdx.x, (int)gridDim.x, part);
 }
 
 __global__ __launch_bounds__(64) void rays_at_pixels_bwd_finish_kernel(const float *partials, int n_parts, float *g_c2w) {
@@ -1044,24 +1018,16 @@ __global__ __launch_bounds__(64) void rays_at_pixels_bwd_finish_kernel(const flo
     g_c2w[threadIdx.x] = t;
 }
 
-int launch_rays_at_pixels_bwd(const double *K4, const int32_t *pix, int64_t n, const float *g_o, const float *g_d, float *g_c2w,
+int launch_rays_at_pixels_bwd(const double *K4, const int32_t *pix, int64_t n, int B, const float *g_o, const float *g_d, float *g_c2w,
                               float *partials, hipStream_t s) {
-    if (n <= 0) return hipMemsetAsync(g_c2w, 0, 12 * sizeof(float), s) == hipSuccess ? NERF_AMD_OK : NERF_AMD_EHIP;
-    int64_t blocks = (n + RAYS_AT_BWD_PER_BLOCK - 1) / RAYS_AT_BWD_PER_BLOCK;
-    if (blocks > RAYS_AT_BWD_MAX_BLOCKS) blocks = RAYS_AT_BWD_MAX_BLOCKS;
-    if (blocks > 1 && !partials) return NERF_AMD_EINVAL;
-    const PixCam k = {(float)K4[0], (float)K4[1], (float)K4[2], (float)K4[3]};
-    hipLaunchKernelGGL(rays_at_pixels_bwd_kernel, dim3((unsigned)blocks), dim3(RAP_BLOCK), 0, s, k, pix, n, g_o, g_d, g_c2w, partials);
-    if (blocks > 1) hipLaunchKernelGGL(rays_at_pixels_bwd_finish_kernel, dim3(1), dim3(64), 0, s, partials, (int)blocks, g_c2w);
-    return hipGetLastError() == hipSuccess ? NERF_AMD_OK : NERF_AMD_EHIP;
-}
-
-int launch_rays_at_pixels_batch_bwd(const double *K4, const int32_t *pix, int64_t n, int B, const float *g_o, const float *g_d,
-                                    float *g_c2w, hipStream_t s) {
-    if (B < 1 || B > POSE_BATCH_MAX || n > RAYS_AT_BWD_PER_BLOCK) return NERF_AMD_EINVAL;
+    if (B < 1 || B > POSE_BATCH_MAX) return NERF_AMD_EINVAL;
+    const int blocks = reduce_blocks(n, RAYS_AT_BWD_PER_BLOCK, RAYS_AT_BWD_MAX_BLOCKS);
+    if (blocks > 1 && (!partials || B > 1)) return NERF_AMD_EINVAL;
     if (n <= 0) return hipMemsetAsync(g_c2w, 0, (size_t)B * 12 * sizeof(float), s) == hipSuccess ? NERF_AMD_OK : NERF_AMD_EHIP;
     const PixCam k = {(float)K4[0], (float)K4[1], (float)K4[2], (float)K4[3]};
-    hipLaunchKernelGGL(rays_at_pixels_batch_bwd_kernel, dim3((unsigned)B), dim3(RAP_BLOCK), 0, s, k, pix, n, g_o, g_d, g_c2w);
+    hipLaunchKernelGGL(rays_at_pixels_bwd_kernel, dim3((unsigned)blocks, (unsigned)B), dim3(RAP_BLOCK), 0, s, k, pix, n, g_o, g_d, g_c2w,
+                       partials);
+    if (blocks > 1) hipLaunchKernelGGL(rays_at_pixels_bwd_finish_kernel, dim3(1), dim3(64), 0, s, partials, blocks, g_c2w);
     return hipGetLastError() == hipSuccess ? NERF_AMD_OK : NERF_AMD_EHIP;
 }
 
@@ -1117,14 +1083,10 @@ __device__ __forceinline__ void se3_forward(const float *w, const float *v, cons
         }
 }
 
-__global__ __launch_bounds__(64) void se3_transform_kernel(const float *w, const float *v, const float *theta, const float *x, float *T) {
-    if (threadIdx.x != 0) return;
-    se3_forward(w, v, theta, x, T);
-}
-
 // B hypotheses, one lane each (lane b of the grid's waves): w, v [B, 3], theta [B], x at b * x_stride (0 = shared), T [B, 16].
-__global__ __launch_bounds__(64) void se3_transform_batch_kernel(const float *w, const float *v, const float *theta, const float *x,
-                                                                 int x_stride, int B, float *T) {
+// The module of one pose is B = 1.
+__global__ __launch_bounds__(64) void se3_transform_kernel(const float *w, const float *v, const float *theta, const float *x,
+                                                           int x_stride, int B, float *T) {
     const int b = blockIdx.x * 64 + threadIdx.x;
     if (b >= B) return;
     se3_forward(w + 3 * b, v + 3 * b, theta + b, x + b * x_stride, T + 16 * b);
@@ -1168,42 +1130,25 @@ __device__ __forceinline__ void se3_backward(const float *w, const float *v, con
 }
 
 __global__ __launch_bounds__(64) void se3_transform_bwd_kernel(const float *w, const float *v, const float *theta, const float *x,
-                                                               const float *g_T, float *g_w, float *g_v, float *g_theta) {
-    if (threadIdx.x != 0) return;
-    se3_backward(w, v, theta, x, g_T, g_w, g_v, g_theta);
-}
-
-__global__ __launch_bounds__(64) void se3_transform_batch_bwd_kernel(const float *w, const float *v, const float *theta, const float *x,
-                                                                     int x_stride, int B, const float *g_T, float *g_w, float *g_v,
-                                                                     float *g_theta) {
+                                                               int x_stride, int B, const float *g_T, float *g_w, float *g_v,
+                                                               float *g_theta) {
     const int b = blockIdx.x * 64 + threadIdx.x;
     if (b >= B) return;
     se3_backward(w + 3 * b, v + 3 * b, theta + b, x + b * x_stride, g_T + 16 * b, g_w + 3 * b, g_v + 3 * b, g_theta + b);
 }
 
-int launch_se3_transform(const float *w, const float *v, const float *theta, const float *x, float *T, hipStream_t s) {
-    hipLaunchKernelGGL(se3_transform_kernel, dim3(1), dim3(64), 0, s, w, v, theta, x, T);
-    return hipGetLastError() == hipSuccess ? NERF_AMD_OK : NERF_AMD_EHIP;
-}
-
-int launch_se3_transform_bwd(const float *w, const float *v, const float *theta, const float *x, const float *g_T, float *g_w,
-                             float *g_v, float *g_theta, hipStream_t s) {
-    hipLaunchKernelGGL(se3_transform_bwd_kernel, dim3(1), dim3(64), 0, s, w, v, theta, x, g_T, g_w, g_v, g_theta);
-    return hipGetLastError() == hipSuccess ? NERF_AMD_OK : NERF_AMD_EHIP;
-}
-
-int launch_se3_transform_batch(const float *w, const float *v, const float *theta, const float *x, int x_stride, int B, float *T,
-                               hipStream_t s) {
+int launch_se3_transform(const float *w, const float *v, const float *theta, const float *x, int x_stride, int B, float *T,
+                         hipStream_t s) {
     if (B < 1 || B > POSE_BATCH_MAX || (x_stride != 0 && x_stride != 16)) return NERF_AMD_EINVAL;
-    hipLaunchKernelGGL(se3_transform_batch_kernel, dim3((unsigned)((B + 63) / 64)), dim3(64), 0, s, w, v, theta, x, x_stride, B, T);
+    hipLaunchKernelGGL(se3_transform_kernel, dim3((unsigned)((B + 63) / 64)), dim3(64), 0, s, w, v, theta, x, x_stride, B, T);
     return hipGetLastError() == hipSuccess ? NERF_AMD_OK : NERF_AMD_EHIP;
 }
 
-int launch_se3_transform_batch_bwd(const float *w, const float *v, const float *theta, const float *x, int x_stride, int B,
-                                   const float *g_T, float *g_w, float *g_v, float *g_theta, hipStream_t s) {
+int launch_se3_transform_bwd(const float *w, const float *v, const float *theta, const float *x, int x_stride, int B, const float *g_T,
+                             float *g_w, float *g_v, float *g_theta, hipStream_t s) {
     if (B < 1 || B > POSE_BATCH_MAX || (x_stride != 0 && x_stride != 16)) return NERF_AMD_EINVAL;
-    hipLaunchKernelGGL(se3_transform_batch_bwd_kernel, dim3((unsigned)((B + 63) / 64)), dim3(64), 0, s, w, v, theta, x, x_stride, B, g_T,
-                       g_w, g_v, g_theta);
+    hipLaunchKernelGGL(se3_transform_bwd_kernel, dim3((unsigned)((B + 63) / 64)), dim3(64), 0, s, w, v, theta, x, x_stride, B, g_T, g_w,
+                       g_v, g_theta);
     return hipGetLastError() == hipSuccess ? NERF_AMD_OK : NERF_AMD_EHIP;
 }
 

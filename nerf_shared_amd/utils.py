@@ -194,16 +194,18 @@ def get_rays(H, W, K, c2w):
 
 
 class _RaysAtPixelsFn(torch.autograd.Function):
-    """get_rays_at with a HIP backward with respect to the pose (nerf_amd_rays_at_pixels_backward); nothing touches the host."""
+    """get_rays_at with a HIP backward with respect to the pose; nothing touches the host.  c2w [3|4, 4] is B = 1 of c2w
+    [B, 3|4, 4]: the rank is looked at HERE (no indexing node enters the graph) and outputs and gradient have the caller's rank."""
 
     @staticmethod
     def forward(ctx, c2w, pix, H, W, K4):
-        dev, n = c2w.device, pix.shape[0]
-        o, d = torch.empty(n, 3, device=dev, dtype=torch.float32), torch.empty(n, 3, device=dev, dtype=torch.float32)
+        dev, n, lead = c2w.device, pix.shape[0], tuple(c2w.shape[:-2])
+        o, d = torch.empty(*lead, n, 3, device=dev, dtype=torch.float32), torch.empty(*lead, n, 3, device=dev, dtype=torch.float32)
         k4 = (ctypes.c_double * 4)(*K4)
         with torch.cuda.device(dev):
-            _lib.check(lib.nerf_amd_rays_at_pixels(H, W, k4, c2w.data_ptr(), c2w.stride(0), pix.data_ptr(), n, o.data_ptr(),
-                                                   d.data_ptr(), _lib.stream_of(dev)), "nerf_amd_rays_at_pixels")
+            _lib.check(lib.nerf_amd_rays_at_pixels_batch(H, W, k4, c2w.data_ptr(), c2w.stride(0) if lead else 0, c2w.stride(-2),
+                                                         lead[0] if lead else 1, pix.data_ptr(), n, o.data_ptr(), d.data_ptr(),
+                                                         _lib.stream_of(dev)), "nerf_amd_rays_at_pixels_batch")
         ctx.meta = (H, W, K4, tuple(c2w.shape))
         ctx.pix = pix
         return o, d
@@ -215,49 +217,25 @@ class _RaysAtPixelsFn(torch.autograd.Function):
         dev, n = pix.device, pix.shape[0]
         g_o = None if g_o is None else g_o.contiguous().float()
         g_d = None if g_d is None else g_d.contiguous().float()
-        # the kernel overwrites the first 12 floats = rows 0..2; row 3 of a [4,4] pose gets no gradient
-        g = torch.zeros(shape, device=dev, dtype=torch.float32) if shape[0] > 3 else torch.empty(shape, device=dev, dtype=torch.float32)
-        partials = torch.empty(256 * 12, device=dev, dtype=torch.float32) if n > 16384 else None
         k4 = (ctypes.c_double * 4)(*K4)
         with torch.cuda.device(dev):
-            _lib.check(lib.nerf_amd_rays_at_pixels_backward(H, W, k4, pix.data_ptr(), n, _lib.ptr(g_o), _lib.ptr(g_d), g.data_ptr(),
-                                                            _lib.ptr(partials), _lib.stream_of(dev)), "nerf_amd_rays_at_pixels_backward")
-        return g, None, None, None, None
-
-
-class _RaysAtPixelsBatchFn(torch.autograd.Function):
-    """get_rays_at for B poses at shared pixels (nerf_amd_rays_at_pixels_batch and its backward, one block per hypothesis)."""
-
-    @staticmethod
-    def forward(ctx, c2w, pix, H, W, K4):
-        dev, B, n = c2w.device, c2w.shape[0], pix.shape[0]
-        o, d = torch.empty(B, n, 3, device=dev, dtype=torch.float32), torch.empty(B, n, 3, device=dev, dtype=torch.float32)
-        k4 = (ctypes.c_double * 4)(*K4)
-        with torch.cuda.device(dev):
-            _lib.check(lib.nerf_amd_rays_at_pixels_batch(H, W, k4, c2w.data_ptr(), c2w.stride(0), c2w.stride(1), B, pix.data_ptr(), n,
-                                                         o.data_ptr(), d.data_ptr(), _lib.stream_of(dev)), "nerf_amd_rays_at_pixels_batch")
-        ctx.meta = (H, W, K4, tuple(c2w.shape))
-        ctx.pix = pix
-        return o, d
-
-    @staticmethod
-    def backward(ctx, g_o, g_d):
-        H, W, K4, shape = ctx.meta
-        pix = ctx.pix
-        dev, n, B = pix.device, pix.shape[0], shape[0]
-        g_o = None if g_o is None else g_o.contiguous().float()
-        g_d = None if g_d is None else g_d.contiguous().float()
-        out = torch.empty(B, 3, 4, device=dev, dtype=torch.float32)
-        k4 = (ctypes.c_double * 4)(*K4)
-        with torch.cuda.device(dev):
-            _lib.check(lib.nerf_amd_rays_at_pixels_batch_backward(H, W, k4, pix.data_ptr(), n, B, _lib.ptr(g_o), _lib.ptr(g_d),
-                                                                  out.data_ptr(), _lib.stream_of(dev)),
+            if len(shape) == 2:
+                # one pose: any n (several blocks and `partials` beyond 16384).  The kernel overwrites the first 12 floats =
+                # rows 0..2; row 3 of a [4, 4] pose gets no gradient
+                g = torch.zeros(shape, device=dev, dtype=torch.float32) if shape[0] > 3 else torch.empty(shape, device=dev, dtype=torch.float32)
+                partials = torch.empty(256 * 12, device=dev, dtype=torch.float32) if n > 16384 else None
+                _lib.check(lib.nerf_amd_rays_at_pixels_backward(H, W, k4, pix.data_ptr(), n, _lib.ptr(g_o), _lib.ptr(g_d), g.data_ptr(),
+                                                                _lib.ptr(partials), _lib.stream_of(dev)), "nerf_amd_rays_at_pixels_backward")
+                return g, None, None, None, None
+            g = torch.empty(shape[0], 3, 4, device=dev, dtype=torch.float32)
+            _lib.check(lib.nerf_amd_rays_at_pixels_batch_backward(H, W, k4, pix.data_ptr(), n, shape[0], _lib.ptr(g_o), _lib.ptr(g_d),
+                                                                  g.data_ptr(), _lib.stream_of(dev)),
                        "nerf_amd_rays_at_pixels_batch_backward")
         if shape[1] > 3:                           # row 3 of a [4, 4] pose gets no gradient
+            rows = g
             g = torch.zeros(shape, device=dev, dtype=torch.float32)
-            g[:, :3] = out
-            out = g
-        return out, None, None, None, None
+            g[:, :3] = rows
+        return g, None, None, None, None
 
 
 def _device_pixels(pixels, H, W, device):
@@ -291,19 +269,14 @@ def get_rays_at(H, W, K, c2w, pixels):
     bit-equal to get_rays_at(H, W, K, c2w[b], pixels); the backward is one block per hypothesis (n <= 16384)."""
     if not (isinstance(c2w, torch.Tensor) and c2w.is_cuda):
         raise _lib.NerfAmdError("get_rays_at reads the pose on the device: c2w must be a ROCm tensor (utils.get_rays takes host poses)")
-    if c2w.dim() == 3:
-        if c2w.shape[1] not in (3, 4) or c2w.shape[2] != 4 or not 1 <= c2w.shape[0] <= POSE_BATCH_MAX:
-            raise _lib.NerfAmdError("a pose batch must be [B, 3, 4] or [B, 4, 4] with 1 <= B <= %d, got %s" % (POSE_BATCH_MAX, tuple(c2w.shape)))
-        pose = c2w if (c2w.dtype == torch.float32 and c2w.stride(2) == 1 and c2w.stride(1) >= 4 and c2w.stride(0) >= 0) \
-            else c2w.float().contiguous()
-        pix = _device_pixels(pixels, int(H), int(W), pose.device)
-        K4 = (float(K[0][0]), float(K[1][1]), float(K[0][2]), float(K[1][2]))
-        if not (pose.requires_grad and torch.is_grad_enabled()):
-            pose = pose.detach()
-        return _RaysAtPixelsBatchFn.apply(pose, pix, int(H), int(W), K4)
-    if c2w.dim() != 2 or c2w.shape[0] not in (3, 4) or c2w.shape[1] != 4:
+    batch = c2w.dim() == 3
+    if batch and (c2w.shape[1] not in (3, 4) or c2w.shape[2] != 4 or not 1 <= c2w.shape[0] <= POSE_BATCH_MAX):
+        raise _lib.NerfAmdError("a pose batch must be [B, 3, 4] or [B, 4, 4] with 1 <= B <= %d, got %s" % (POSE_BATCH_MAX, tuple(c2w.shape)))
+    if not batch and (c2w.dim() != 2 or c2w.shape[0] not in (3, 4) or c2w.shape[1] != 4):
         raise _lib.NerfAmdError("c2w must be [3, 4] or [4, 4], got %s" % (tuple(c2w.shape),))
-    pose = c2w if (c2w.dtype == torch.float32 and c2w.stride(1) == 1 and c2w.stride(0) >= 4) else c2w.float().contiguous()
+    # already usable strides (rows of >= 4 floats with unit stride inside, poses at any non-negative distance): no copy
+    usable = c2w.dtype == torch.float32 and c2w.stride(-1) == 1 and c2w.stride(-2) >= 4 and (not batch or c2w.stride(0) >= 0)
+    pose = c2w if usable else c2w.float().contiguous()
     pix = _device_pixels(pixels, int(H), int(W), pose.device)
     K4 = (float(K[0][0]), float(K[1][1]), float(K[0][2]), float(K[1][2]))
     if not (pose.requires_grad and torch.is_grad_enabled()):
@@ -312,27 +285,43 @@ def get_rays_at(H, W, K, c2w, pixels):
 
 
 class _Se3Fn(torch.autograd.Function):
-    """T = exp_i(w, v, theta) x (nerf_amd_se3_transform): one launch forward, one backward; x is a constant."""
+    """T[b] = exp_i(w[b], v[b], theta[b]) x_b (nerf_amd_se3_transform_batch): one launch forward, one backward; x is a constant.
+    w, v [3] and theta [] are B = 1 of w, v [B, 3] and theta [B] (contiguous): T and the gradients have the caller's shapes."""
 
     @staticmethod
     def forward(ctx, w, v, theta, x):
-        T = torch.empty(4, 4, device=x.device, dtype=torch.float32)
+        T = torch.empty(*theta.shape, 4, 4, device=x.device, dtype=torch.float32)
+        ctx.x_stride = 16 if x.dim() == 3 else 0
         with torch.cuda.device(x.device):
-            _lib.check(lib.nerf_amd_se3_transform(w.data_ptr(), v.data_ptr(), theta.data_ptr(), x.data_ptr(), T.data_ptr(),
-                                                  _lib.stream_of(x.device)), "nerf_amd_se3_transform")
+            _lib.check(lib.nerf_amd_se3_transform_batch(w.data_ptr(), v.data_ptr(), theta.data_ptr(), x.data_ptr(), ctx.x_stride,
+                                                        theta.numel(), T.data_ptr(), _lib.stream_of(x.device)),
+                       "nerf_amd_se3_transform_batch")
         ctx.save_for_backward(w, v, theta, x)
         return T
 
     @staticmethod
     def backward(ctx, g_T):
         w, v, theta, x = ctx.saved_tensors
-        g = torch.empty(7, device=x.device, dtype=torch.float32)
+        B = theta.numel()
+        g = torch.empty(7 * B, device=x.device, dtype=torch.float32)             # g_w [B, 3] | g_v [B, 3] | g_theta [B]
         g_T = g_T.contiguous().float()
         with torch.cuda.device(x.device):
-            _lib.check(lib.nerf_amd_se3_transform_backward(w.data_ptr(), v.data_ptr(), theta.data_ptr(), x.data_ptr(), g_T.data_ptr(),
-                                                           g.data_ptr(), g.data_ptr() + 12, g.data_ptr() + 24,
-                                                           _lib.stream_of(x.device)), "nerf_amd_se3_transform_backward")
-        return g[0:3], g[3:6], g[6].reshape(theta.shape), None
+            _lib.check(lib.nerf_amd_se3_transform_batch_backward(w.data_ptr(), v.data_ptr(), theta.data_ptr(), x.data_ptr(), ctx.x_stride,
+                                                                 B, g_T.data_ptr(), g.data_ptr(), g.data_ptr() + 12 * B,
+                                                                 g.data_ptr() + 24 * B, _lib.stream_of(x.device)),
+                       "nerf_amd_se3_transform_batch_backward")
+        return g[:3 * B].view(w.shape), g[3 * B:6 * B].view(v.shape), g[6 * B:].view(theta.shape), None
+
+
+def _se3_apply(module, x):
+    """The end of CameraTransf.forward and CameraTransfBatch.forward (x's shape is checked): the device and dtype refusals,
+    then the one Function."""
+    me = type(module).__name__
+    _lib.require_device(x, "x")
+    _lib.require_device(module.w, "%s's parameters" % me)
+    if any(p.dtype != torch.float32 or p.device != x.device or not p.is_contiguous() for p in (module.w, module.v, module.theta)):
+        raise _lib.NerfAmdError("%s's parameters must be contiguous fp32 on the pose's device (%s)" % (me, x.device))
+    return _Se3Fn.apply(module.w, module.v, module.theta, x.detach().float().contiguous())
 
 
 class CameraTransf(torch.nn.Module):
@@ -353,41 +342,9 @@ class CameraTransf(torch.nn.Module):
         self.theta = torch.nn.Parameter(torch.normal(0., 1e-6, size=()))
 
     def forward(self, x):
-        _lib.require_device(x, "x")
-        _lib.require_device(self.w, "CameraTransf's parameters")
         if tuple(x.shape) != (4, 4):
             raise _lib.NerfAmdError("CameraTransf takes a [4, 4] pose, got %s" % (tuple(x.shape),))
-        if any(p.dtype != torch.float32 or p.device != x.device for p in (self.w, self.v, self.theta)):
-            raise _lib.NerfAmdError("CameraTransf's parameters must be fp32 on the pose's device (%s)" % x.device)
-        return _Se3Fn.apply(self.w, self.v, self.theta, x.detach().float().contiguous())
-
-
-class _Se3BatchFn(torch.autograd.Function):
-    """T[b] = exp_i(w[b], v[b], theta[b]) x_b (nerf_amd_se3_transform_batch): one launch each way; x is a constant."""
-
-    @staticmethod
-    def forward(ctx, w, v, theta, x):
-        B = w.shape[0]
-        T = torch.empty(B, 4, 4, device=x.device, dtype=torch.float32)
-        ctx.x_stride = 16 if x.dim() == 3 else 0
-        with torch.cuda.device(x.device):
-            _lib.check(lib.nerf_amd_se3_transform_batch(w.data_ptr(), v.data_ptr(), theta.data_ptr(), x.data_ptr(), ctx.x_stride, B,
-                                                        T.data_ptr(), _lib.stream_of(x.device)), "nerf_amd_se3_transform_batch")
-        ctx.save_for_backward(w, v, theta, x)
-        return T
-
-    @staticmethod
-    def backward(ctx, g_T):
-        w, v, theta, x = ctx.saved_tensors
-        B = w.shape[0]
-        g = torch.empty(7 * B, device=x.device, dtype=torch.float32)
-        g_T = g_T.contiguous().float()
-        with torch.cuda.device(x.device):
-            _lib.check(lib.nerf_amd_se3_transform_batch_backward(w.data_ptr(), v.data_ptr(), theta.data_ptr(), x.data_ptr(), ctx.x_stride,
-                                                                 B, g_T.data_ptr(), g.data_ptr(), g.data_ptr() + 12 * B,
-                                                                 g.data_ptr() + 24 * B, _lib.stream_of(x.device)),
-                       "nerf_amd_se3_transform_batch_backward")
-        return g[:3 * B].view(B, 3), g[3 * B:6 * B].view(B, 3), g[6 * B:], None
+        return _se3_apply(self, x)
 
 
 class CameraTransfBatch(torch.nn.Module):
@@ -412,13 +369,9 @@ class CameraTransfBatch(torch.nn.Module):
 
     def forward(self, x):
         B = self.n_poses
-        _lib.require_device(x, "x")
-        _lib.require_device(self.w, "CameraTransfBatch's parameters")
         if tuple(x.shape) not in ((4, 4), (B, 4, 4)):
             raise _lib.NerfAmdError("CameraTransfBatch(%d) takes a [4, 4] or [%d, 4, 4] pose, got %s" % (B, B, tuple(x.shape)))
-        if any(p.dtype != torch.float32 or p.device != x.device or not p.is_contiguous() for p in (self.w, self.v, self.theta)):
-            raise _lib.NerfAmdError("CameraTransfBatch's parameters must be contiguous fp32 on the pose's device (%s)" % x.device)
-        return _Se3BatchFn.apply(self.w, self.v, self.theta, x.detach().float().contiguous())
+        return _se3_apply(self, x)
 
     def pose_module(self, b):
         """A CameraTransf holding COPIES of hypothesis b's seven numbers (on their device): the way to go on with the winner
@@ -749,7 +702,32 @@ def _capture_step(body, optimizer, params, repack_models, dev, warmup):
     return graph
 
 
-class CapturedTrainStep:
+class _CapturedStep:
+    """What the captured steps share: the optimizer they accept, and a call's tail (learning rate, replay, stale weights).
+    A subclass sets self.graph (from _capture_step) and self.loss (in its captured body)."""
+
+    _ADAM_OVER = "(utils.get_optimizer)"          # where the message says the optimizer comes from
+
+    def _take_optimizer(self, optimizer):
+        from . import optim
+        if not isinstance(optimizer, optim.Adam):
+            raise _lib.NerfAmdError("%s needs nerf_shared_amd.optim.Adam %s: torch's optimizers pass step-dependent scalars as "
+                                    "kernel arguments, which a graph would freeze" % (type(self).__name__, self._ADAM_OVER))
+        self.optimizer = optimizer
+        self.params = [p for g in optimizer.param_groups for p in g["params"]]
+        self._lr = None
+
+    def _replay(self):
+        lr = tuple(float(g["lr"]) for g in self.optimizer.param_groups)
+        if lr != self._lr:
+            self.optimizer.sync_lr()
+            self._lr = lr
+        self.graph.replay()
+        self.optimizer.note_replayed_step()
+        return self.loss
+
+
+class CapturedTrainStep(_CapturedStep):
     """One iteration of the reference's training loop (main.py:77-104: render_from_rays -> img2mse(rgb) [+ img2mse(rgb0)]
     -> loss.backward() -> optimizer.step()) captured once in a HIP graph and replayed.
 
@@ -777,19 +755,14 @@ class CapturedTrainStep:
     """
 
     def __init__(self, renderer, H, W, K, chunk, coarse_model, fine_model, optimizer, n_rays, warmup=3):
-        from . import optim
-        if not isinstance(optimizer, optim.Adam):
-            raise _lib.NerfAmdError("CapturedTrainStep needs nerf_shared_amd.optim.Adam (utils.get_optimizer): torch's optimizers "
-                                    "pass step-dependent scalars as kernel arguments, which a graph would freeze")
+        self._take_optimizer(optimizer)
         dev = next(coarse_model.parameters()).device
-        self.renderer, self.models, self.optimizer = renderer, (coarse_model, fine_model), optimizer
+        self.renderer, self.models = renderer, (coarse_model, fine_model)
         self.args = (H, W, K, chunk)
         self.rays = torch.zeros(2, n_rays, 3, device=dev)
         self.rays[1, :, 2] = -1.0                     # a valid placeholder batch for the warm-up (zero directions have no unit vector)
         self.target = torch.full((n_rays, 3), 0.5, device=dev)
-        self.params = [p for g in optimizer.param_groups for p in g["params"]]
         self.loss = self.psnr = None
-        self._lr = None
         self.graph = _capture_step(self._body, optimizer, self.params, self.models, dev, warmup)
 
     def _body(self):
@@ -809,16 +782,10 @@ class CapturedTrainStep:
     def __call__(self, rays, target):
         self.rays.copy_(rays if isinstance(rays, torch.Tensor) else torch.stack(list(rays), 0), non_blocking=True)
         self.target.copy_(target, non_blocking=True)
-        lr = tuple(float(g["lr"]) for g in self.optimizer.param_groups)
-        if lr != self._lr:
-            self.optimizer.sync_lr()
-            self._lr = lr
-        self.graph.replay()
-        self.optimizer.note_replayed_step()
-        return self.loss
+        return self._replay()
 
 
-class CapturedPoseStep:
+class CapturedPoseStep(_CapturedStep):
     """One iteration of the pose-estimation demo's loop (demo_est_rel_pose.py:74-98) captured once in a HIP graph and replayed:
 
         pose = cam_transf(start_pose) -> get_rays_at(H, W, K, pose, pixels) -> render_from_rays -> img2mse(rgb, target)
@@ -852,24 +819,22 @@ class CapturedPoseStep:
     warm-up draws of the construction do not count: sampler.draw_count is afterwards what it was before.
     """
 
+    _ADAM_OVER = "over cam_transf.parameters()"
+
     def __init__(self, renderer, H, W, K, chunk, coarse_model, fine_model, cam_transf, start_pose, optimizer, n_rays, warmup=3,
                  sampler=None):
-        from . import optim
         me = type(self).__name__                  # (CapturedMultiPoseStep shares this constructor)
-        if not isinstance(optimizer, optim.Adam):
-            raise _lib.NerfAmdError("%s needs nerf_shared_amd.optim.Adam over cam_transf.parameters(): torch's "
-                                    "optimizers pass step-dependent scalars as kernel arguments, which a graph would freeze" % me)
+        self._take_optimizer(optimizer)
         for name, m in (("coarse_model", coarse_model), ("fine_model", fine_model)):
             if m is not None and any(p.requires_grad for p in m.parameters()):
                 raise _lib.NerfAmdError("%s optimises the pose against FROZEN fields: call %s.requires_grad_(False) "
                                         "(its parameters ask for gradients that this step would compute and nobody would use)" % (me, name))
-        self.params = [p for g in optimizer.param_groups for p in g["params"]]
         mine = {id(p) for p in cam_transf.parameters()}
         if not self.params or {id(p) for p in self.params} != mine:
             raise _lib.NerfAmdError("%s: the optimizer must hold exactly cam_transf's parameters (w, v, theta)" % me)
         dev = self.params[0].device
         _lib.require_device(self.params[0], "cam_transf's parameters")
-        self.renderer, self.models, self.cam_transf, self.optimizer = renderer, (coarse_model, fine_model), cam_transf, optimizer
+        self.renderer, self.models, self.cam_transf = renderer, (coarse_model, fine_model), cam_transf
         self.args = (int(H), int(W), K, chunk)
         self.start_pose = torch.as_tensor(start_pose, dtype=torch.float32).to(dev).contiguous().clone()
         self._check_start_pose()
@@ -887,7 +852,6 @@ class CapturedPoseStep:
             self.pixels = torch.zeros(n_rays, 2, device=dev, dtype=torch.int32)
             self.target = torch.full((n_rays, 3), 0.5, device=dev)
         self.loss = self.pose = None
-        self._lr = None
         self.graph = _capture_step(self._body, optimizer, self.params, (), dev, warmup)
         if sampler is not None:
             sampler.draw_count.copy_(draws_before)                # the warm-up draws do not count
@@ -907,14 +871,21 @@ class CapturedPoseStep:
             self.sampler.draw()                   # fills self.pixels / self.target (the sampler's buffers)
         pose = self.cam_transf(self.start_pose)
         rays_o, rays_d = get_rays_at(H, W, K, pose, self.pixels)
-        rgb, disp, acc, extras = self.renderer.render_from_rays(H, W, K, chunk, torch.stack([rays_o, rays_d], 0), coarse, fine,
+        rgb, disp, acc, extras = self.renderer.render_from_rays(H, W, K, chunk, self._renderer_rays(rays_o, rays_d), coarse, fine,
                                                                 retraw=True)
-        loss = img2mse(rgb, self.target)          # the demo's loss is the fine pass alone (demo_est_rel_pose.py:92)
-        loss.backward()
+        self.loss = self._loss_backward(rgb)
         self.optimizer.step()
-        self.loss = loss.detach()
         with torch.no_grad():
             self.pose = self.cam_transf(self.start_pose)
+
+    # what differs between one pose and B hypotheses in the body: the rays' shape for the renderer, and the loss
+    def _renderer_rays(self, rays_o, rays_d):
+        return torch.stack([rays_o, rays_d], 0)
+
+    def _loss_backward(self, rgb):
+        loss = img2mse(rgb, self.target)          # the demo's loss is the fine pass alone (demo_est_rel_pose.py:92)
+        loss.backward()
+        return loss.detach()
 
     def __call__(self, pixels=None, target=None):
         H, W = self.args[0], self.args[1]
@@ -927,13 +898,7 @@ class CapturedPoseStep:
             pix = pixels if (isinstance(pixels, torch.Tensor) and pixels.is_cuda) else _device_pixels(pixels, H, W, self.pixels.device)
             self.pixels.copy_(pix, non_blocking=True)
             self.target.copy_(target, non_blocking=True)
-        lr = tuple(float(g["lr"]) for g in self.optimizer.param_groups)
-        if lr != self._lr:
-            self.optimizer.sync_lr()
-            self._lr = lr
-        self.graph.replay()
-        self.optimizer.note_replayed_step()
-        return self.loss
+        return self._replay()
 
 
 class CapturedMultiPoseStep(CapturedPoseStep):
@@ -978,24 +943,14 @@ class CapturedMultiPoseStep(CapturedPoseStep):
             raise _lib.NerfAmdError("start_poses must be [%d, 4, 4] (the module's hypotheses) or [4, 4], got %s"
                                     % (B, tuple(self.start_pose.shape)))
 
-    def _body(self):
-        H, W, K, chunk = self.args
-        coarse, fine = self.models
-        B, n = self.cam_transf.n_poses, self.pixels.shape[0]
-        for p in self.params:
-            p.grad = None
-        if self.sampler is not None:
-            self.sampler.draw()
-        poses = self.cam_transf(self.start_pose)
-        rays_o, rays_d = get_rays_at(H, W, K, poses, self.pixels)
-        rays = torch.stack([rays_o.view(B * n, 3), rays_d.view(B * n, 3)], 0)
-        rgb, disp, acc, extras = self.renderer.render_from_rays(H, W, K, chunk, rays, coarse, fine, retraw=True)
-        losses = img2mse_each(rgb.reshape(B, n, 3), self.target)
+    def _renderer_rays(self, rays_o, rays_d):     # [B, n, 3] each -> hypothesis-major rows
+        Bn = self.cam_transf.n_poses * self.pixels.shape[0]
+        return torch.stack([rays_o.view(Bn, 3), rays_d.view(Bn, 3)], 0)
+
+    def _loss_backward(self, rgb):
+        losses = img2mse_each(rgb.reshape(self.cam_transf.n_poses, self.pixels.shape[0], 3), self.target)
         losses.sum().backward()
-        self.optimizer.step()
-        self.loss = losses.detach()
-        with torch.no_grad():
-            self.pose = self.cam_transf(self.start_pose)
+        return losses.detach()
 
 
 def multistart_scores(losses, window=10):
@@ -1063,21 +1018,30 @@ def estimate_relative_pose(coarse_model, fine_model, renderer, sensor_image, sta
     be frozen (requires_grad_(False)), as CapturedPoseStep demands; `points` are the caller's interest points (cv2 SIFT's, as
     in the demo) instead of the built-in detector's; `seed` fixes the draws.  (The returned tuple also carries `.step`, the
     captured step, for going on from there.)"""
+    step, losses = _estimate_poses(CapturedPoseStep, CameraTransf, start_pose, chunk, (), coarse_model, fine_model, renderer,
+                                   sensor_image, K, steps, batch_size, lrate, strategy, kernel_size, dil_iter, points, seed)
+    return PoseEstimate(step.pose.clone(), losses, step)
+
+
+def _estimate_poses(step_type, make_cam_transf, start, chunk, loss_shape, coarse_model, fine_model, renderer, sensor_image, K, steps,
+                    batch_size, lrate, strategy, kernel_size, dil_iter, points, seed):
+    """The loop of estimate_relative_pose and estimate_relative_pose_multistart: the sampler, the se(3) module that
+    `make_cam_transf()` builds, Adam over it, one captured step of `step_type`, and `steps` replays with the demo's
+    schedule.  Returns (step, losses [steps, *loss_shape])."""
     from . import optim
     H, W = int(sensor_image.shape[0]), int(sensor_image.shape[1])
     dev = next(coarse_model.parameters()).device
     sampler = PixelSampler(sensor_image, batch_size, strategy=strategy, points=points, kernel_size=kernel_size, dil_iter=dil_iter,
                            seed=seed, device=dev)
-    cam_transf = CameraTransf().to(dev)
+    cam_transf = make_cam_transf().to(dev)
     optimizer = optim.Adam(cam_transf.parameters(), lr=lrate, betas=(0.9, 0.999))
-    step = CapturedPoseStep(renderer, H, W, K, chunk, coarse_model, fine_model, cam_transf, start_pose, optimizer, batch_size,
-                            sampler=sampler)
-    losses = torch.zeros(int(steps), device=dev, dtype=torch.float32)
+    step = step_type(renderer, H, W, K, chunk, coarse_model, fine_model, cam_transf, start, optimizer, batch_size, sampler=sampler)
+    losses = torch.zeros(int(steps), *loss_shape, device=dev, dtype=torch.float32)
     for k in range(int(steps)):
         losses[k].copy_(step())
         for g in optimizer.param_groups:
             g['lr'] = lrate * (0.8 ** ((k + 1) / 100))
-    return PoseEstimate(step.pose.clone(), losses, step)
+    return step, losses
 
 
 class MultiPoseEstimate(PoseEstimate):
@@ -1101,24 +1065,13 @@ def estimate_relative_pose_multistart(coarse_model, fine_model, renderer, sensor
 
     Returns (pose, losses) with pose = poses[best] (device [4, 4]) and losses [steps, B] (device); the tuple also carries
     .poses [B, 4, 4], .scores [B], .best (0-dim device int64) and .step (go on with step.cam_transfs.pose_module(int(best)))."""
-    from . import optim
-    H, W = int(sensor_image.shape[0]), int(sensor_image.shape[1])
-    dev = next(coarse_model.parameters()).device
     start_poses = torch.as_tensor(start_poses, dtype=torch.float32)
     if start_poses.dim() != 3 or tuple(start_poses.shape[1:]) != (4, 4):
         raise _lib.NerfAmdError("start_poses must be [B, 4, 4], got %s" % (tuple(start_poses.shape),))
     B = start_poses.shape[0]
-    sampler = PixelSampler(sensor_image, batch_size, strategy=strategy, points=points, kernel_size=kernel_size, dil_iter=dil_iter,
-                           seed=seed, device=dev)
-    cam_transfs = CameraTransfBatch(B).to(dev)
-    optimizer = optim.Adam(cam_transfs.parameters(), lr=lrate, betas=(0.9, 0.999))
-    step = CapturedMultiPoseStep(renderer, H, W, K, max(int(chunk), B * int(batch_size)), coarse_model, fine_model, cam_transfs,
-                                 start_poses, optimizer, batch_size, sampler=sampler)
-    losses = torch.zeros(int(steps), B, device=dev, dtype=torch.float32)
-    for k in range(int(steps)):
-        losses[k].copy_(step())
-        for g in optimizer.param_groups:
-            g['lr'] = lrate * (0.8 ** ((k + 1) / 100))
+    step, losses = _estimate_poses(CapturedMultiPoseStep, lambda: CameraTransfBatch(B), start_poses, max(int(chunk), B * int(batch_size)),
+                                   (B,), coarse_model, fine_model, renderer, sensor_image, K, steps, batch_size, lrate, strategy,
+                                   kernel_size, dil_iter, points, seed)
     scores, best = multistart_scores(losses, window)
     poses = step.poses.clone()
     return MultiPoseEstimate(poses.index_select(0, best.reshape(1))[0], losses, step, poses, scores, best)

@@ -18,7 +18,7 @@ pytestmark = pytest.mark.gpu
 
 from nerf_shared_amd import _lib, synth  # noqa: E402
 from test_gpu_backward import BASE, VD  # noqa: E402
-from test_gpu_pose_step import TWIST, frozen_pair, lego44, pixel_cases, se3_params, se3_torch  # noqa: E402
+from test_gpu_pose_step import TWIST, frozen_pair, lego44, pixel_cases, pose_grad_reference, se3_params, se3_torch  # noqa: E402
 
 LOCKSTEP_REPEATS = 3
 EINVAL = -1
@@ -233,6 +233,92 @@ def test_loss_batch_beyond_one_block(dev):
     assert bool(torch.isnan(res).all()) and bool(torch.isnan(gx).all())
     # the last size inside the limit goes through the library
     assert type(utils.img2mse_each(x[:, :16384].contiguous(), y[:16384].contiguous()).grad_fn).__name__.startswith("_Img2MseEachFn")
+
+
+# ------------------------------------------------------------------------------------------------ one pose is B = 1 of each op
+# The single-pose and the batch entry points launch the same kernels.  What must NOT follow from that: the batch entry points
+# pass no `partials`, so at B = 1 they keep their one-block limits, and the single entry points keep theirs.
+_RNG16K1 = np.random.default_rng(161)
+PIX_16385 = np.stack([_RNG16K1.integers(0, 800, size=16385), _RNG16K1.integers(0, 800, size=16385)], -1)
+
+
+def test_b1_does_not_open_the_batch_entry_points_past_their_limits(dev):
+    """B = 1 with 16385 values per hypothesis: EINVAL from all three batch entry points that have a limit, nothing launched
+    (the outputs keep their NaN fill)."""
+    L = _lib.lib
+    n = m = 16385
+    pix = torch.from_numpy(PIX_16385).to(device=dev, dtype=torch.int32).contiguous()
+    g = torch.ones(1, n, 3, device=dev)
+    rc, out = rays_bwd_batch(dev, 800, 800, pix, 1, g, g)
+    assert rc == EINVAL and b"16384" in L.nerf_amd_last_error()
+    x, y = torch.rand(1, m, device=dev), torch.rand(m, device=dev)
+    res, gx = torch.full((1,), float("nan"), device=dev), torch.full((1, m), float("nan"), device=dev)
+    one = torch.ones(1, device=dev)
+    for y_stride in (0, m):
+        assert L.nerf_amd_img2mse_each(x.data_ptr(), y.data_ptr(), y_stride, m, 1, res.data_ptr(), _lib.stream_of(dev)) == EINVAL
+        assert b"16384" in L.nerf_amd_last_error()
+        assert L.nerf_amd_img2mse_each_backward(x.data_ptr(), y.data_ptr(), y_stride, m, 1, one.data_ptr(), gx.data_ptr(),
+                                                _lib.stream_of(dev)) == EINVAL
+        assert b"16384" in L.nerf_amd_last_error()
+    torch.cuda.synchronize()
+    assert bool(torch.isnan(out).all()) and bool(torch.isnan(res).all()) and bool(torch.isnan(gx).all())
+
+
+def rays_bwd_single_16385(dev, pix, g_o, g_d, partials):
+    """nerf_amd_rays_at_pixels_backward over PIX_16385 -> (rc, g_c2w [12] prefilled with NaN)."""
+    out = torch.full((12,), float("nan"), device=dev)
+    rc = _lib.lib.nerf_amd_rays_at_pixels_backward(800, 800, k4_of(800, 800), pix.data_ptr(), pix.shape[0], _lib.ptr(g_o), _lib.ptr(g_d),
+                                                   out.data_ptr(), _lib.ptr(partials), _lib.stream_of(dev))
+    return rc, out
+
+
+def test_single_rays_backward_at_16385_needs_partials_and_is_the_float64_sum(dev):
+    """Two blocks: without `partials` EINVAL and nothing launched; with them, and with either gradient null, the float64 sum
+    within the bound of test_rays_at_pixels_backward_is_the_float64_sum_and_order_fixed (1e-5 of the sum of |terms| per entry),
+    and two calls give equal bits."""
+    n = PIX_16385.shape[0]
+    rng = np.random.default_rng(n)
+    g_o_np, g_d_np = rng.normal(size=(n, 3)).astype(np.float32), rng.normal(size=(n, 3)).astype(np.float32)
+    pix = torch.from_numpy(PIX_16385).to(device=dev, dtype=torch.int32).contiguous()
+    g_o, g_d = torch.from_numpy(g_o_np).to(dev), torch.from_numpy(g_d_np).to(dev)
+    rc, out = rays_bwd_single_16385(dev, pix, g_o, g_d, None)
+    torch.cuda.synchronize()
+    assert rc == EINVAL and bool(torch.isnan(out).all())
+    assert b"needs the partials buffer" in _lib.lib.nerf_amd_last_error()
+    partials = torch.empty(256 * 12, device=dev)
+    for tag, (a, c) in {"g_o=None": (None, g_d), "g_d=None": (g_o, None)}.items():
+        rc, out = rays_bwd_single_16385(dev, pix, a, c, partials)
+        assert rc == 0, (tag, _lib.lib.nerf_amd_last_error())
+        got = out.cpu().double().numpy().reshape(3, 4)
+        ref, mag = pose_grad_reference(800, 800, PIX_16385, None if a is None else g_o_np, None if c is None else g_d_np)
+        err = np.abs(got - ref)
+        print("n16385 %s: worst |got - ref| / sum|terms| = %.3e" % (tag, float((err / np.maximum(mag, 1e-300)).max())))
+        assert np.isfinite(got).all() and (err <= 1e-5 * mag).all(), (tag, got, ref)
+        rc, again = rays_bwd_single_16385(dev, pix, a, c, partials)
+        assert rc == 0 and torch.equal(out, again), tag
+
+
+def test_a_1x4x4_pose_and_a_4x4_pose_give_equal_rays_and_gradients(dev):
+    """get_rays_at with a [1, 4, 4] and with a [4, 4] pose that requires grad, 5 pixels of a 20 x 20 image: rays and pose
+    gradient equal bit for bit, each in its caller's shape, and row 3 of both gradients zero."""
+    from nerf_shared_amd import utils
+    Hs = Ws = 20
+    K = synth.lego_intrinsics(Hs, Ws)
+    pix = torch.tensor([[0, 0], [19, 19], [7, 3], [3, 7], [7, 3]], dtype=torch.int32, device=dev)
+    rng = np.random.default_rng(44)
+    co = torch.from_numpy(rng.normal(size=(5, 3)).astype(np.float32)).to(dev)
+    cd = torch.from_numpy(rng.normal(size=(5, 3)).astype(np.float32)).to(dev)
+    one = torch.from_numpy(lego44()).to(dev).requires_grad_(True)
+    batch = torch.from_numpy(lego44()[None].copy()).to(dev).requires_grad_(True)
+    o1, d1 = utils.get_rays_at(Hs, Ws, K, one, pix)
+    oB, dB = utils.get_rays_at(Hs, Ws, K, batch, pix)
+    assert o1.shape == d1.shape == (5, 3) and oB.shape == dB.shape == (1, 5, 3)
+    assert torch.equal(oB[0], o1) and torch.equal(dB[0], d1)
+    ((o1 * co).sum() + (d1 * cd).sum()).backward()
+    ((oB[0] * co).sum() + (dB[0] * cd).sum()).backward()
+    assert one.grad.shape == (4, 4) and batch.grad.shape == (1, 4, 4)
+    assert torch.equal(batch.grad[0], one.grad) and float(one.grad[:3].abs().max()) > 0
+    assert not bool(one.grad[3].any()) and not bool(batch.grad[0, 3].any())
 
 
 # ------------------------------------------------------------------------------------------------ the scene of tests 4 to 8
