@@ -499,6 +499,101 @@ int nerf_amd_dilate_mask(const uint8_t *in, int32_t H, int32_t W, int32_t k, int
 int nerf_amd_compact_mask(const uint8_t *mask, int32_t H, int32_t W, int32_t *block_counts, int32_t *list, int64_t *count,
                           void *stream);
 
+/* ------------------------------------------------------------------------
+ * Occupancy grid: render without evaluating the field in empty space.  OPT-IN: nothing above reads a grid.
+ * Plain loads / stores, integer arithmetic and fp32 operations rounded one by one (no contraction), no float atomics and
+ * no atomics on the grid (one thread writes each whole 32-bit word), so every result below is DEFINED exactly and tests
+ * compare for equality.
+ *
+ * The grid is an axis-aligned box lo[3] < hi[3] (finite) with resolution n[3], each 1..1024, in the coordinates the field
+ * is evaluated in (for NDC-warped rays: NDC coordinates, e.g. a box around [-1, 1]^3).  Cell (ix, iy, iz) has the linear
+ * index c = (ix n[1] + iy) n[2] + iz and is bit (c & 31) of int32 word (c >> 5) of `words` (DEVICE,
+ * (n[0] n[1] n[2] + 31) / 32 words; the unused bits of the last word are 0).
+ * Lookup of a point p, per axis a, in fp32 with two rounded operations:
+ *   t_a = (p_a - lo_a) * scale_a,   scale_a = float32(n_a / (hi_a - lo_a)) formed in double on the host and rounded once,
+ *   i_a = floor(t_a);   p is OUTSIDE when on any axis !(t_a >= 0 && t_a < n_a) (this includes NaN), else in cell (i_x, i_y, i_z).
+ * An outside point is live under NERF_AMD_OCC_OUTSIDE_LIVE (conservative: the grid only ever removes points it covers) and
+ * dead under NERF_AMD_OCC_OUTSIDE_EMPTY (a bounded object, such as the Blender scenes); an inside point is live when its bit is set.
+ * Every entry point refuses (NERF_AMD_EINVAL) a grid outside these limits.
+ * ------------------------------------------------------------------------ */
+#define NERF_AMD_OCC_OUTSIDE_LIVE  0
+#define NERF_AMD_OCC_OUTSIDE_EMPTY 1
+typedef struct nerf_amd_occupancy_grid {
+    const int32_t *words;      /* DEVICE bit words; may be NULL where only the geometry is read (sample_points) */
+    float   lo[3], hi[3];
+    int32_t n[3];
+    int32_t outside;           /* NERF_AMD_OCC_OUTSIDE_* */
+} nerf_amd_occupancy_grid;
+
+/* The lookup alone: pts [n,3] fp32 DEVICE -> live [n] uint8 (1 / 0) and, unless NULL, cell [n] int32 (c, or -1 outside). */
+int nerf_amd_occupancy_query(const nerf_amd_occupancy_grid *grid, const float *pts, int64_t n, uint8_t *live, int32_t *cell,
+                             void *stream);
+
+/* K sample points in each of the cells [c0, c1): pts [(c1 - c0) K, 3], sample j of cell c at row (c - c0) K + j.
+ * Per axis a:  p_a = lo_a + (i_a + f_a) * w_a  (two rounded fp32 operations; i_a + f_a is exact),
+ *   w_a = float32((hi_a - lo_a) / n_a) formed in double on the host and rounded once,
+ *   sample 0 is the cell centre, f = (0.5, 0.5, 0.5);  samples j >= 1 are a keyed-hash jitter on an 8-bit lattice:
+ *   h = mix(mix(seed + 0x9e3779b9 j) ^ c)     (uint32 mod 2^32; mix() as defined for nerf_amd_draw_pixels above)
+ *   f_x = ((h & 255) + 0.5) / 256,  f_y = (((h >> 8) & 255) + 0.5) / 256,  f_z = (((h >> 16) & 255) + 0.5) / 256,
+ * so a sample lies at least 1/512 of a cell from every face of its cell, and it LOOKS UP TO ITS OWN CELL: the rounding
+ * errors of forming p and of the lookup add up to less than 2^-11 of a cell wherever
+ *   max(|lo_a|, |hi_a|) n_a / (hi_a - lo_a) <= 4096   on every axis
+ * (a box within a few thousand cell widths of the origin); a grid beyond that is refused here (NERF_AMD_EINVAL).
+ * 0 <= c0 <= c1 <= n[0] n[1] n[2], K >= 1, (c1 - c0) K < 2^31. */
+int nerf_amd_occupancy_sample_points(const nerf_amd_occupancy_grid *grid, int64_t c0, int64_t c1, int32_t K, uint32_t seed,
+                                     float *pts, void *stream);
+
+/* Sets the bits of the cells [c0, c1) from sigma [(c1 - c0) K] (the density at the rows of sample_points):
+ * bit c = any_j(sigma[(c - c0) K + j] > threshold); NaN compares false.  c0 is a multiple of 32, so every word belongs to one
+ * thread; the bits of a touched word beyond c1 become 0 (accumulate == 0) or stay (accumulate != 0).  With accumulate != 0
+ * the new bits are ORed into the words -- how a second model is added to a grid. */
+int nerf_amd_occupancy_mark(const float *sigma, int64_t c0, int64_t c1, int32_t K, float threshold, int accumulate,
+                            int32_t *words, void *stream);
+
+/* `iterations` rounds of 3 x 3 x 3 box dilation of the bits of an nx x ny x nz grid, in -> out (DEVICE words, distinct):
+ * one round sets a cell when any of its 27 neighbours (itself included) is set, off-grid neighbours ignored.  The rounds
+ * compose into one maximum over the (2 iterations + 1)^3 window, which is what is computed; 0 iterations copy.
+ * The unused bits of the last word of `out` are 0. */
+int nerf_amd_occupancy_dilate(const int32_t *in, int32_t nx, int32_t ny, int32_t nz, int32_t iterations, int32_t *out,
+                              void *stream);
+
+/* The per-view kernel: which sample points of rays [R, 8|11] at depths z [R,S] are live.  Point r S + s is
+ * rays_o + rays_d z, the product rounded before the sum -- the two operations of the field kernels in their rays + z_vals
+ * mode, so the bits are theirs -- looked up as above.  Written stably, in point order:
+ *   rank [R S] int32: the position of the point in the compact list, or -1 if culled;
+ *   pts_live [*count, 3] (room for R S rows);  vd_live [*count, 3] = the ray's view direction (columns 8..10), when
+ *   ray_ch == 11 (else NULL);  *count int64 DEVICE.
+ * Three launches -- counts per 256 points, one scan, write at rank -- and no atomics.
+ * block_counts: (R S + 255) / 256 int32 of DEVICE scratch.  R S < 2^31. */
+int nerf_amd_occupancy_cull(const nerf_amd_occupancy_grid *grid, const float *rays, int32_t ray_ch, const float *z, int64_t R,
+                            int32_t S, int32_t *block_counts, int32_t *rank, float *pts_live, float *vd_live, int64_t *count,
+                            void *stream);
+
+/* The inverse: raw [n, ch] from raw_live [*, ch] and rank [n]: row i = raw_live[rank[i]], or +0.0 in every channel where
+ * rank[i] < 0 (a zero sigma gives alpha 0 and weight 0 in raw2outputs).  One thread per dense row, no memset. */
+int nerf_amd_occupancy_expand(const float *raw_live, const int32_t *rank, int64_t n, int32_t ch, float *raw, void *stream);
+
+/* The field at a point list: pts [n,3], viewdirs [n,3] (one per POINT; NULL for a model without view branch) -> raw [n,ch].
+ * Unlike nerf_amd_nerf_forward it takes the RENDER path's choice of weight stream (tuning key 2: the folded stream of a
+ * bf16 view-branch model when NERF_AMD_COPY_BF16_FOLD is current), so a compacted pass runs the kernel the dense pass
+ * runs and live rows are bit-equal to the dense ones.  n == 0 returns NERF_AMD_OK and launches nothing.  n < 2^31. */
+int nerf_amd_field_points(const nerf_amd_model *m, const float *pts, const float *viewdirs, int64_t n, float *raw,
+                          int precision, void *stream);
+
+/* nerf_amd_render_rays with the field evaluated at live points only: each pass is cull -> live count to the host ->
+ * nerf_amd_field_points on the compact list -> expand, and everything else (z_vals, compositing, resampling) is the
+ * dense code on a dense raw, so outputs have the usual layout; culled samples have raw = +0.0.
+ * SYNCHRONISES: the live count has to size the field launch, so each pass copies 8 bytes into pinned host memory and
+ * waits for `stream` (once with N_importance == 0, twice otherwise).  It therefore CANNOT be captured in a graph (a
+ * capturing stream is refused) and blocks the calling thread.  A pass with no live point launches no field kernel.
+ * cfg->use_noise is refused (NERF_AMD_EINVAL): sigma noise would resurrect culled samples.
+ * io->workspace: nerf_amd_render_rays_culled_workspace(cfg, R, out_ch) bytes (a pure host function; -1 for bad arguments).
+ * stats: HOST int64 [4] or NULL <- {live, total} points of the coarse pass, {live, total} of the fine pass (0, 0 without one). */
+int64_t nerf_amd_render_rays_culled_workspace(const nerf_amd_render_cfg *cfg, int64_t R, int32_t out_ch);
+int     nerf_amd_render_rays_culled(const nerf_amd_render_cfg *cfg, const nerf_amd_model *coarse, const nerf_amd_model *fine,
+                                    const nerf_amd_render_io *io, int64_t R, const nerf_amd_occupancy_grid *grid,
+                                    int64_t *stats, void *stream);
+
 /* Image output stage: utils.to8b (utils.py:30) as used by Renderer.render_from_batch_poses
  * (render_utils.py:312): out[i] = uint8(255 * clip(x[i], 0, 1)), truncating; NaN -> 0.
  * x [n] fp32 DEVICE (16-byte aligned), out [n] uint8 DEVICE (4-byte aligned). */

@@ -41,7 +41,11 @@ EXPORTS = (
     "nerf_amd_density_value_grad",
     "nerf_amd_draw_pixels", "nerf_amd_interest_points_workspace", "nerf_amd_interest_points", "nerf_amd_dilate_mask",
     "nerf_amd_compact_mask",
+    "nerf_amd_occupancy_query", "nerf_amd_occupancy_sample_points", "nerf_amd_occupancy_mark", "nerf_amd_occupancy_dilate",
+    "nerf_amd_occupancy_cull", "nerf_amd_occupancy_expand", "nerf_amd_field_points",
+    "nerf_amd_render_rays_culled_workspace", "nerf_amd_render_rays_culled",
 )
+OCC_OUTSIDE_LIVE, OCC_OUTSIDE_EMPTY = 0, 1
 
 
 class Arch(Structure):
@@ -63,6 +67,10 @@ class RenderIO(Structure):
                 ("rgb0", c_void_p), ("disp0", c_void_p), ("acc0", c_void_p),
                 ("z_std", c_void_p), ("raw", c_void_p), ("weights", c_void_p), ("z_vals", c_void_p),
                 ("workspace", c_void_p), ("workspace_bytes", c_int64)]
+
+
+class OccupancyGridC(Structure):
+    _fields_ = [("words", c_void_p), ("lo", c_float * 3), ("hi", c_float * 3), ("n", c_int32 * 3), ("outside", c_int32)]
 
 
 def _load():
@@ -144,6 +152,17 @@ def _load():
         "nerf_amd_interest_points": (c_int, [c_void_p, c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p]),
         "nerf_amd_dilate_mask": (c_int, [c_void_p, c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p]),
         "nerf_amd_compact_mask": (c_int, [c_void_p, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p]),
+        "nerf_amd_occupancy_query": (c_int, [POINTER(OccupancyGridC), c_void_p, c_int64, c_void_p, c_void_p, c_void_p]),
+        "nerf_amd_occupancy_sample_points": (c_int, [POINTER(OccupancyGridC), c_int64, c_int64, c_int32, c_uint32, c_void_p, c_void_p]),
+        "nerf_amd_occupancy_mark": (c_int, [c_void_p, c_int64, c_int64, c_int32, c_float, c_int, c_void_p, c_void_p]),
+        "nerf_amd_occupancy_dilate": (c_int, [c_void_p, c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p]),
+        "nerf_amd_occupancy_cull": (c_int, [POINTER(OccupancyGridC), c_void_p, c_int32, c_void_p, c_int64, c_int32, c_void_p, c_void_p,
+                                            c_void_p, c_void_p, c_void_p, c_void_p]),
+        "nerf_amd_occupancy_expand": (c_int, [c_void_p, c_void_p, c_int64, c_int32, c_void_p, c_void_p]),
+        "nerf_amd_field_points": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_int, c_void_p]),
+        "nerf_amd_render_rays_culled_workspace": (c_int64, [POINTER(RenderCfg), c_int64, c_int32]),
+        "nerf_amd_render_rays_culled": (c_int, [POINTER(RenderCfg), c_void_p, c_void_p, POINTER(RenderIO), c_int64,
+                                                POINTER(OccupancyGridC), POINTER(c_int64), c_void_p]),
         "nerf_amd_get_rays_backward": (c_int, [c_int32, c_int32, POINTER(c_double), c_int64, c_int64, c_void_p, c_void_p,
                                                c_void_p, c_void_p]),
         "nerf_amd_to8b": (c_int, [c_void_p, c_int64, c_void_p, c_void_p]),

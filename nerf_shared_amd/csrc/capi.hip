@@ -920,6 +920,197 @@ int nerf_amd_render_chunks(const nerf_amd_render_cfg *cfg, const nerf_amd_model 
 
 }  // extern "C"
 
+// ---- occupancy grid (occupancy.hip): the grid's entry points, the field at a point list, render_rays over live points ----
+namespace {
+constexpr double OCC_SAMPLE_REACH = 4096.0;      // nerf_amd_occupancy_sample_points: max(|lo|, |hi|) n / (hi - lo) it vouches for
+
+// the caller's grid, checked, as the kernels take it
+int occ_grid(const nerf_amd_occupancy_grid *g, bool need_words, OccGrid *out) {
+    if (!g) return fail(NERF_AMD_EINVAL, "null occupancy grid");
+    if (need_words && !g->words) return fail(NERF_AMD_EINVAL, "occupancy grid has no words");
+    if (g->outside != NERF_AMD_OCC_OUTSIDE_LIVE && g->outside != NERF_AMD_OCC_OUTSIDE_EMPTY)
+        return fail(NERF_AMD_EINVAL, "occupancy grid: unknown outside policy");
+    out->words = g->words;
+    out->outside_live = g->outside == NERF_AMD_OCC_OUTSIDE_LIVE;
+    for (int a = 0; a < 3; ++a) {
+        if (g->n[a] < 1 || g->n[a] > 1024) return fail(NERF_AMD_EINVAL, "occupancy grid: resolution must be 1..1024 per axis");
+        const double lo = g->lo[a], hi = g->hi[a];
+        if (!std::isfinite(lo) || !std::isfinite(hi) || !(hi > lo)) return fail(NERF_AMD_EINVAL, "occupancy grid: box must be finite with lo < hi");
+        out->lo[a] = g->lo[a];
+        out->n[a] = g->n[a];
+        out->scale[a] = (float)((double)g->n[a] / (hi - lo));
+        out->width[a] = (float)((hi - lo) / (double)g->n[a]);
+        if (!std::isfinite(out->scale[a]) || !(out->width[a] > 0.0f)) return fail(NERF_AMD_EINVAL, "occupancy grid: box too thin or too wide for fp32");
+    }
+    return NERF_AMD_OK;
+}
+
+int64_t occ_cells(const int32_t n[3]) { return (int64_t)n[0] * n[1] * n[2]; }
+
+// the field at a point list, with the render path's choice of weight stream (stage_field)
+int field_points(const nerf_amd_model *m, const float *pts, const float *viewdirs, int64_t n, float *raw, int precision, hipStream_t s) {
+    if (n == 0) return NERF_AMD_OK;
+    const int fold_wanted = g_fold.load(std::memory_order_relaxed) != 1 ? FOLD_IF_CURRENT : FOLD_NEVER;
+    MlpArgs a{};
+    set_inputs(a, pts, viewdirs, nullptr, 0, nullptr, true);      // (run_field drops viewdirs for a model without view branch)
+    a.P = n; a.S = 1; a.out = raw;
+    return run_field(m, a, precision, s, fold_wanted);
+}
+
+// scratch of the culled passes behind the dense workspace: one pass's worth, reused by the second
+struct CullWs {
+    int32_t *rank, *block_counts;
+    float *pts, *vd, *raw_live;
+    int64_t *count;
+};
+size_t cull_ws_bytes(int64_t P, int och, CullWs *w, char *base) {
+    size_t b = 0;
+    auto take = [&](size_t bytes) { char *q = base ? base + b : nullptr; b += align_up(bytes); return q; };
+    char *rank = take(P * sizeof(int32_t)), *bc = take(((P + 255) / 256) * sizeof(int32_t)), *pts = take(P * 3 * sizeof(float));
+    char *vd = take(P * 3 * sizeof(float)), *rl = take(P * (size_t)och * sizeof(float)), *cnt = take(sizeof(int64_t));
+    if (w) {
+        w->rank = reinterpret_cast<int32_t *>(rank); w->block_counts = reinterpret_cast<int32_t *>(bc);
+        w->pts = reinterpret_cast<float *>(pts); w->vd = reinterpret_cast<float *>(vd); w->raw_live = reinterpret_cast<float *>(rl);
+        w->count = reinterpret_cast<int64_t *>(cnt);
+    }
+    return b;
+}
+
+// 8 bytes of pinned host memory per host thread for the live count (portable: any device may write it); kept for the
+// life of the process
+int64_t *pinned_count() {
+    thread_local int64_t *p = nullptr;
+    if (!p && hipHostMalloc(reinterpret_cast<void **>(&p), sizeof(int64_t), hipHostMallocPortable) != hipSuccess) p = nullptr;
+    return p;
+}
+
+// stage_field over the live points of the pass: cull -> count to the host -> field on the compact list -> expand
+int stage_field_culled(const ChunkPlan &p, bool fine_pass, const OccGrid &g, const CullWs &w, int64_t *n_live, hipStream_t s) {
+    const int S = fine_pass ? p.Nf : p.Nc;
+    const float *z = fine_pass ? p.z_f : p.z_c;
+    float *raw = fine_pass ? p.raw_f : p.raw_c;
+    const nerf_amd_model *m = fine_pass ? p.fm : p.coarse;
+    int rc = launch_occupancy_cull(g, p.io->rays, p.io->ray_ch, z, p.R, S, w.block_counts, w.rank, w.pts, p.has_vd ? w.vd : nullptr,
+                                   w.count, s);
+    if (rc) return fail(rc, "occupancy cull launch failed");
+    int64_t *host = pinned_count();
+    if (!host) return fail(NERF_AMD_ENOMEM, "no pinned host memory for the live count");
+    HIP_TRY(hipMemcpyAsync(host, w.count, sizeof(int64_t), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    *n_live = *host;
+    if (*n_live < 0 || *n_live > p.R * (int64_t)S) return fail(NERF_AMD_EHIP, "occupancy cull returned an impossible count");
+    if ((rc = field_points(m, w.pts, p.has_vd ? w.vd : nullptr, *n_live, w.raw_live, p.cfg->precision, s))) return rc;
+    rc = launch_occupancy_expand(w.raw_live, w.rank, p.R * (int64_t)S, p.och, raw, s);
+    return rc ? fail(rc, "occupancy expand launch failed") : NERF_AMD_OK;
+}
+}  // namespace
+
+extern "C" {
+
+int nerf_amd_occupancy_query(const nerf_amd_occupancy_grid *grid, const float *pts, int64_t n, uint8_t *live, int32_t *cell,
+                             void *stream) {
+    OccGrid g;
+    if (int rc = occ_grid(grid, true, &g)) return rc;
+    if (n < 0 || (n > 0 && (!pts || !live))) return fail(NERF_AMD_EINVAL, "bad occupancy_query arguments");
+    int rc = launch_occupancy_query(g, pts, n, live, cell, static_cast<hipStream_t>(stream));
+    return rc ? fail(rc, "occupancy_query launch failed") : NERF_AMD_OK;
+}
+
+int nerf_amd_occupancy_sample_points(const nerf_amd_occupancy_grid *grid, int64_t c0, int64_t c1, int32_t K, uint32_t seed,
+                                     float *pts, void *stream) {
+    OccGrid g;
+    if (int rc = occ_grid(grid, false, &g)) return rc;
+    for (int a = 0; a < 3; ++a) {
+        const double lo = grid->lo[a], hi = grid->hi[a];
+        if (std::fmax(std::fabs(lo), std::fabs(hi)) * grid->n[a] / (hi - lo) > OCC_SAMPLE_REACH)
+            return fail(NERF_AMD_EINVAL, "occupancy_sample_points: the box is too far from the origin for its cell size "
+                                         "(max(|lo|, |hi|) n / (hi - lo) must not exceed 4096): samples could leave their cells");
+    }
+    if (c0 < 0 || c1 < c0 || c1 > occ_cells(grid->n) || K < 1 || (c1 - c0) * (int64_t)K >= ((int64_t)1 << 31) || (c1 > c0 && !pts))
+        return fail(NERF_AMD_EINVAL, "bad occupancy_sample_points arguments");
+    int rc = launch_occupancy_sample_points(g, c0, c1, K, seed, pts, static_cast<hipStream_t>(stream));
+    return rc ? fail(rc, "occupancy_sample_points launch failed") : NERF_AMD_OK;
+}
+
+int nerf_amd_occupancy_mark(const float *sigma, int64_t c0, int64_t c1, int32_t K, float threshold, int accumulate,
+                            int32_t *words, void *stream) {
+    if (c0 < 0 || (c0 & 31) || c1 < c0 || c1 > ((int64_t)1 << 30) || K < 1 || (c1 - c0) * (int64_t)K >= ((int64_t)1 << 31) ||
+        (c1 > c0 && (!sigma || !words)))
+        return fail(NERF_AMD_EINVAL, "bad occupancy_mark arguments (c0 must be a multiple of 32)");
+    int rc = launch_occupancy_mark(sigma, c0, c1, K, threshold, accumulate, words, static_cast<hipStream_t>(stream));
+    return rc ? fail(rc, "occupancy_mark launch failed") : NERF_AMD_OK;
+}
+
+int nerf_amd_occupancy_dilate(const int32_t *in, int32_t nx, int32_t ny, int32_t nz, int32_t iterations, int32_t *out,
+                              void *stream) {
+    if (nx < 1 || ny < 1 || nz < 1 || nx > 1024 || ny > 1024 || nz > 1024 || iterations < 0 || !in || !out || in == out)
+        return fail(NERF_AMD_EINVAL, "bad occupancy_dilate arguments");
+    int rc = launch_occupancy_dilate(in, nx, ny, nz, iterations > 1024 ? 1024 : iterations, out, static_cast<hipStream_t>(stream));
+    return rc ? fail(rc, "occupancy_dilate launch failed") : NERF_AMD_OK;
+}
+
+int nerf_amd_occupancy_cull(const nerf_amd_occupancy_grid *grid, const float *rays, int32_t ray_ch, const float *z, int64_t R,
+                            int32_t S, int32_t *block_counts, int32_t *rank, float *pts_live, float *vd_live, int64_t *count,
+                            void *stream) {
+    OccGrid g;
+    if (int rc = occ_grid(grid, true, &g)) return rc;
+    if (R < 0 || S < 1 || (ray_ch != 8 && ray_ch != 11) || R * (int64_t)S >= ((int64_t)1 << 31) || !count ||
+        (R > 0 && (!rays || !z || !block_counts || !rank || !pts_live)) || (vd_live && ray_ch != 11))
+        return fail(NERF_AMD_EINVAL, "bad occupancy_cull arguments");
+    int rc = launch_occupancy_cull(g, rays, ray_ch, z, R, S, block_counts, rank, pts_live, vd_live, count, static_cast<hipStream_t>(stream));
+    return rc ? fail(rc, "occupancy_cull launch failed") : NERF_AMD_OK;
+}
+
+int nerf_amd_occupancy_expand(const float *raw_live, const int32_t *rank, int64_t n, int32_t ch, float *raw, void *stream) {
+    if (n < 0 || ch < 1 || (n > 0 && (!rank || !raw))) return fail(NERF_AMD_EINVAL, "bad occupancy_expand arguments");
+    int rc = launch_occupancy_expand(raw_live, rank, n, ch, raw, static_cast<hipStream_t>(stream));
+    return rc ? fail(rc, "occupancy_expand launch failed") : NERF_AMD_OK;
+}
+
+int nerf_amd_field_points(const nerf_amd_model *m, const float *pts, const float *viewdirs, int64_t n, float *raw,
+                          int precision, void *stream) {
+    if (!m || n < 0) return fail(NERF_AMD_EINVAL, "bad field_points arguments");
+    if (n == 0) return NERF_AMD_OK;
+    if (!pts || !raw) return fail(NERF_AMD_EINVAL, "null pts/raw");
+    return field_points(m, pts, viewdirs, n, raw, precision, static_cast<hipStream_t>(stream));
+}
+
+int64_t nerf_amd_render_rays_culled_workspace(const nerf_amd_render_cfg *cfg, int64_t R, int32_t out_ch) {
+    const int64_t dense = nerf_amd_render_rays_workspace(cfg, R, out_ch);
+    if (dense < 0 || out_ch < 1 || cfg->N_samples < 1 || cfg->N_importance < 0) return -1;
+    return dense + (int64_t)cull_ws_bytes(R * ((int64_t)cfg->N_samples + cfg->N_importance), out_ch, nullptr, nullptr);
+}
+
+int nerf_amd_render_rays_culled(const nerf_amd_render_cfg *cfg, const nerf_amd_model *coarse, const nerf_amd_model *fine,
+                                const nerf_amd_render_io *io, int64_t R, const nerf_amd_occupancy_grid *grid,
+                                int64_t *stats, void *stream) {
+    if (stats) stats[0] = stats[1] = stats[2] = stats[3] = 0;
+    OccGrid g;
+    if (int rc = occ_grid(grid, true, &g)) return rc;
+    if (cfg && cfg->use_noise) return fail(NERF_AMD_EINVAL, "render_rays_culled: sigma noise would resurrect culled samples (use_noise must be 0)");
+    if (R == 0 && cfg && coarse && io) return NERF_AMD_OK;
+    ChunkPlan p;
+    int rc = plan_chunk(cfg, coarse, fine, io, R, &p);
+    if (rc) return rc;
+    if (R * (int64_t)p.Nf >= ((int64_t)1 << 31)) return fail(NERF_AMD_EINVAL, "render_rays_culled: R * samples must stay below 2^31");
+    if (io->workspace_bytes < nerf_amd_render_rays_culled_workspace(cfg, R, p.och)) return fail(NERF_AMD_EINVAL, "workspace too small");
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    hipStreamCaptureStatus st = hipStreamCaptureStatusNone;
+    if (hipStreamIsCapturing(s, &st) != hipSuccess || st != hipStreamCaptureStatusNone)
+        return fail(NERF_AMD_EINVAL, "render_rays_culled synchronises the stream: it cannot be captured in a graph");
+    CullWs w;
+    cull_ws_bytes(R * (int64_t)p.Nf, p.och, &w, static_cast<char *>(io->workspace) + nerf_amd_render_rays_workspace(cfg, R, p.och));
+    int64_t live = 0;
+    if ((rc = stage_z(p, s)) || (rc = stage_field_culled(p, false, g, w, &live, s))) return rc;
+    if (stats) { stats[0] = live; stats[1] = R * (int64_t)p.Nc; }
+    if (p.Ni == 0) return stage_final(p, s);
+    if ((rc = stage_mid(p, nullptr, s)) || (rc = stage_field_culled(p, true, g, w, &live, s))) return rc;
+    if (stats) { stats[2] = live; stats[3] = R * (int64_t)p.Nf; }
+    return stage_final(p, s);
+}
+
+}  // extern "C"
+
 // ---- Renderer.render_batch as ONE call over contiguous whole-batch buffers -------------------------------------
 namespace {
 constexpr int64_t SUPER_CHUNK_RAYS = 32768;      // rays per launch group (the reference's own default chunk)

@@ -215,5 +215,24 @@ int launch_draw_pixels(int64_t M, int n, uint32_t seed, int64_t *draw_count, con
 int launch_interest_points(const uint8_t *image, int H, int W, int C, int quality, void *workspace, uint8_t *mask, hipStream_t s);
 int launch_dilate_mask(const uint8_t *in, int H, int W, int k, int iterations, uint8_t *out, hipStream_t s);
 int launch_compact_mask(const uint8_t *mask, int H, int W, int32_t *block_counts, int32_t *list, int64_t *count, hipStream_t s);
+// its scan alone: counts of any number of 256-element blocks -> exclusive offsets in place, the total in *count (one block
+// whose threads own runs of the counts, so not limited to one block's worth of blocks)
+int launch_compact_scan(int32_t *block_counts, int n_blocks, int64_t *count, hipStream_t s);
+
+// occupancy.hip (include/nerf_amd.h "Occupancy grid"): the grid as the kernels take it, by value
+struct OccGrid {
+    const int32_t *words;
+    float lo[3], scale[3], width[3];   // scale = float32(n / (hi - lo)), width = float32((hi - lo) / n), each rounded once from double
+    int32_t n[3];
+    int32_t outside_live;
+};
+int launch_occupancy_query(const OccGrid &g, const float *pts, int64_t n, uint8_t *live, int32_t *cell, hipStream_t s);
+int launch_occupancy_sample_points(const OccGrid &g, int64_t c0, int64_t c1, int K, uint32_t seed, float *pts, hipStream_t s);
+int launch_occupancy_mark(const float *sigma, int64_t c0, int64_t c1, int K, float threshold, int accumulate, int32_t *words,
+                          hipStream_t s);
+int launch_occupancy_dilate(const int32_t *in, int nx, int ny, int nz, int reach, int32_t *out, hipStream_t s);
+int launch_occupancy_cull(const OccGrid &g, const float *rays, int ray_ch, const float *z, int64_t R, int S, int32_t *block_counts,
+                          int32_t *rank, float *pts_live, float *vd_live, int64_t *count, hipStream_t s);
+int launch_occupancy_expand(const float *raw_live, const int32_t *rank, int64_t n, int ch, float *raw, hipStream_t s);
 
 }  // namespace na

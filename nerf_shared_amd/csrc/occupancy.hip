@@ -1,0 +1,254 @@
+// occupancy.hip -- the occupancy grid (include/nerf_amd.h "Occupancy grid"): which points reach the field kernels.  The
+// lookup, the sample points a grid is filled from, marking, dilation, the per-view compaction of a pass's sample points and
+// its inverse.  Plain memory-bound kernels: integer arithmetic, loads / stores and fp32 operations rounded one by one (this
+// file is compiled with -ffp-contract=off), no float atomics and no atomics on the grid -- one thread writes each whole
+// word -- so every result is defined exactly and tested for equality, like pixel_select.hip.
+#include <hip/hip_runtime.h>
+
+#include <cstdint>
+
+#include "kernels.h"
+#include "mix32.h"
+#include "pipeline.h"
+
+namespace na {
+
+namespace {
+constexpr int OC_BLOCK = 256;           // 4 waves of 64; also the points per count of the compaction (launch_compact_scan)
+
+inline unsigned blocks_for(int64_t n) { return (unsigned)((n + OC_BLOCK - 1) / OC_BLOCK); }
+inline int launched() { return hipGetLastError() == hipSuccess ? NERF_AMD_OK : NERF_AMD_EHIP; }
+
+// The lookup (nerf_amd.h): the cell of p, or -1 outside.  Two rounded operations per axis; the comparisons are false for NaN.
+__device__ __forceinline__ int cell_of(const OccGrid &g, float px, float py, float pz) {
+    const float p[3] = {px, py, pz};
+    int i[3];
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+        const float d = p[a] - g.lo[a];
+        const float t = d * g.scale[a];
+        if (!(t >= 0.0f && t < (float)g.n[a])) return -1;
+        i[a] = (int)floorf(t);
+    }
+    return (i[0] * g.n[1] + i[1]) * g.n[2] + i[2];
+}
+
+__device__ __forceinline__ bool bit_of(const int32_t *words, int c) { return ((uint32_t)words[c >> 5] >> (c & 31)) & 1u; }
+
+__device__ __forceinline__ bool live_at(const OccGrid &g, int c) { return c < 0 ? g.outside_live != 0 : bit_of(g.words, c); }
+}  // namespace
+
+// ---------------------------------------------------------------------------
+// The lookup alone: one thread per point.
+// ---------------------------------------------------------------------------
+__global__ __launch_bounds__(OC_BLOCK) void occupancy_query_kernel(OccGrid g, const float *pts, int64_t n, uint8_t *live, int32_t *cell) {
+    const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx >= n) return;
+    const int c = cell_of(g, pts[3 * idx], pts[3 * idx + 1], pts[3 * idx + 2]);
+    live[idx] = live_at(g, c) ? 1 : 0;
+    if (cell) cell[idx] = c;
+}
+
+int launch_occupancy_query(const OccGrid &g, const float *pts, int64_t n, uint8_t *live, int32_t *cell, hipStream_t s) {
+    if (n <= 0) return NERF_AMD_OK;
+    hipLaunchKernelGGL(occupancy_query_kernel, dim3(blocks_for(n)), dim3(OC_BLOCK), 0, s, g, pts, n, live, cell);
+    return launched();
+}
+
+// ---------------------------------------------------------------------------
+// Sample points of cells: one thread per (cell, sample).  Sample 0 the centre, the others the keyed 8-bit lattice jitter.
+// ---------------------------------------------------------------------------
+__global__ __launch_bounds__(OC_BLOCK) void occupancy_sample_kernel(OccGrid g, uint32_t c0, int64_t n, int K, uint32_t seed, float *pts) {
+    const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx >= n) return;
+    const uint32_t j = (uint32_t)(idx % K), c = c0 + (uint32_t)(idx / K);
+    const uint32_t nz = (uint32_t)g.n[2], ny = (uint32_t)g.n[1];
+    const uint32_t i[3] = {c / (nz * ny), (c / nz) % ny, c % nz};
+    uint32_t h[3] = {0, 0, 0};
+    if (j > 0) {
+        const uint32_t v = mix32(mix32(seed + 0x9e3779b9u * j) ^ c);
+        h[0] = v & 255u; h[1] = (v >> 8) & 255u; h[2] = (v >> 16) & 255u;
+    }
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+        const float f = j > 0 ? ((float)h[a] + 0.5f) * (1.0f / 256.0f) : 0.5f;      // exact: a multiple of 1/512
+        const float u = ((float)i[a] + f) * g.width[a];                             // (the sum is exact: 19 bits)
+        pts[3 * idx + a] = g.lo[a] + u;
+    }
+}
+
+int launch_occupancy_sample_points(const OccGrid &g, int64_t c0, int64_t c1, int K, uint32_t seed, float *pts, hipStream_t s) {
+    const int64_t n = (c1 - c0) * K;
+    if (n <= 0) return NERF_AMD_OK;
+    hipLaunchKernelGGL(occupancy_sample_kernel, dim3(blocks_for(n)), dim3(OC_BLOCK), 0, s, g, (uint32_t)c0, n, K, seed, pts);
+    return launched();
+}
+
+// ---------------------------------------------------------------------------
+// Marking: one thread per cell decides its bit, a wave's ballot is two whole words (c0 is a multiple of 32 and a block
+// starts a multiple of 64 cells behind it), lanes 0 and 32 store one each.
+// ---------------------------------------------------------------------------
+__global__ __launch_bounds__(OC_BLOCK) void occupancy_mark_kernel(const float *sigma, int64_t c0, int64_t n_cells, int K, float threshold,
+                                                                  int accumulate, int32_t *words) {
+    const int64_t rel = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;          // cell c0 + rel
+    bool on = false;
+    if (rel < n_cells) {
+        const float *row = sigma + rel * K;
+        for (int j = 0; j < K; ++j) on = on || row[j] > threshold;
+    }
+    const uint64_t ballot = __ballot(on);
+    const int lane = threadIdx.x & 63;
+    if ((lane & 31) != 0 || rel >= n_cells) return;                             // (a word whose first cell is past c1 is not touched)
+    const uint32_t bits = (uint32_t)(ballot >> lane);
+    int32_t *w = words + ((c0 + rel) >> 5);
+    if (accumulate) *w = (int32_t)((uint32_t)*w | bits);
+    else *w = (int32_t)bits;
+}
+
+int launch_occupancy_mark(const float *sigma, int64_t c0, int64_t c1, int K, float threshold, int accumulate, int32_t *words,
+                          hipStream_t s) {
+    const int64_t n = c1 - c0;
+    if (n <= 0) return NERF_AMD_OK;
+    hipLaunchKernelGGL(occupancy_mark_kernel, dim3(blocks_for(n)), dim3(OC_BLOCK), 0, s, sigma, c0, n, K, threshold, accumulate, words);
+    return launched();
+}
+
+// ---------------------------------------------------------------------------
+// Dilation: `iterations` rounds of a 3 x 3 x 3 maximum with off-grid cells ignored compose, on a box, into ONE maximum over
+// the window of reach `iterations` (as in pixel_select.hip's dilate_mask_kernel), so one pass computes it.  One thread per
+// output word; the scan of a cell's window stops at the first set bit.
+// ---------------------------------------------------------------------------
+__global__ __launch_bounds__(OC_BLOCK) void occupancy_dilate_kernel(const int32_t *in, int nx, int ny, int nz, int reach, int n_words,
+                                                                    int32_t *out) {
+    const int w = blockIdx.x * blockDim.x + threadIdx.x;
+    if (w >= n_words) return;
+    const int n_cells = nx * ny * nz;
+    uint32_t bits = 0;
+    for (int b = 0; b < 32; ++b) {
+        const int c = 32 * w + b;
+        if (c >= n_cells) break;
+        const int z = c % nz, y = (c / nz) % ny, x = c / (nz * ny);
+        const int x0 = max(x - reach, 0), x1 = min(x + reach, nx - 1), y0 = max(y - reach, 0), y1 = min(y + reach, ny - 1);
+        const int z0 = max(z - reach, 0), z1 = min(z + reach, nz - 1);
+        bool on = false;
+        for (int xx = x0; xx <= x1 && !on; ++xx)
+            for (int yy = y0; yy <= y1 && !on; ++yy) {
+                const int base = (xx * ny + yy) * nz;
+                for (int zz = z0; zz <= z1 && !on; ++zz) on = bit_of(in, base + zz);
+            }
+        if (on) bits |= 1u << b;
+    }
+    out[w] = (int32_t)bits;
+}
+
+int launch_occupancy_dilate(const int32_t *in, int nx, int ny, int nz, int reach, int32_t *out, hipStream_t s) {
+    const int n_words = (int)(((int64_t)nx * ny * nz + 31) / 32);
+    hipLaunchKernelGGL(occupancy_dilate_kernel, dim3(blocks_for(n_words)), dim3(OC_BLOCK), 0, s, in, nx, ny, nz, reach, n_words, out);
+    return launched();
+}
+
+// ---------------------------------------------------------------------------
+// The per-view compaction, after launch_compact_mask: counts per block of 256 points, one scan of the counts, then every
+// live point written at its rank.  Stable (point order) by construction: no atomics.  The count pass leaves each point's
+// verdict in rank[] (0 live, -1 culled), so the grid is read once per point.
+// ---------------------------------------------------------------------------
+__device__ __forceinline__ void sample_point(const float *rays, int ray_ch, const float *z, int64_t idx, int S, float p[3], int64_t *ray) {
+    *ray = idx / S;
+    const float *r = rays + *ray * ray_ch;
+    const float zz = z[idx];
+    p[0] = mul_then_add(r[3], zz, r[0]);          // pts = o + d z, the product rounded first: the field kernels' own two operations
+    p[1] = mul_then_add(r[4], zz, r[1]);
+    p[2] = mul_then_add(r[5], zz, r[2]);
+}
+
+__global__ __launch_bounds__(OC_BLOCK) void occupancy_cull_count_kernel(OccGrid g, const float *rays, int ray_ch, const float *z, int64_t n,
+                                                                        int S, int32_t *rank, int32_t *block_counts) {
+    __shared__ int wave_counts[OC_BLOCK / 64];
+    const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    bool on = false;
+    if (idx < n) {
+        float p[3];
+        int64_t ray;
+        sample_point(rays, ray_ch, z, idx, S, p, &ray);
+        on = live_at(g, cell_of(g, p[0], p[1], p[2]));
+        rank[idx] = on ? 0 : -1;
+    }
+    const uint64_t ballot = __ballot(on);
+    if ((threadIdx.x & 63) == 0) wave_counts[threadIdx.x >> 6] = __popcll(ballot);
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        int c = 0;
+        for (int w = 0; w < OC_BLOCK / 64; ++w) c += wave_counts[w];
+        block_counts[blockIdx.x] = c;
+    }
+}
+
+__global__ __launch_bounds__(OC_BLOCK) void occupancy_cull_write_kernel(const float *rays, int ray_ch, const float *z, int64_t n, int S,
+                                                                        const int32_t *block_offsets, int32_t *rank, float *pts_live,
+                                                                        float *vd_live) {
+    __shared__ int wave_counts[OC_BLOCK / 64];
+    const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const bool on = idx < n && rank[idx] == 0;
+    const uint64_t ballot = __ballot(on);
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    if (lane == 0) wave_counts[wave] = __popcll(ballot);
+    __syncthreads();
+    if (!on) return;
+    int r = block_offsets[blockIdx.x] + __popcll(ballot & (((uint64_t)1 << lane) - 1));
+    for (int w = 0; w < wave; ++w) r += wave_counts[w];
+    rank[idx] = r;
+    float p[3];
+    int64_t ray;
+    sample_point(rays, ray_ch, z, idx, S, p, &ray);
+    float *dst = pts_live + 3 * (int64_t)r;
+    dst[0] = p[0]; dst[1] = p[1]; dst[2] = p[2];
+    if (vd_live) {
+        const float *v = rays + ray * ray_ch + 8;
+        float *dv = vd_live + 3 * (int64_t)r;
+        dv[0] = v[0]; dv[1] = v[1]; dv[2] = v[2];
+    }
+}
+
+int launch_occupancy_cull(const OccGrid &g, const float *rays, int ray_ch, const float *z, int64_t R, int S, int32_t *block_counts,
+                          int32_t *rank, float *pts_live, float *vd_live, int64_t *count, hipStream_t s) {
+    const int64_t n = R * S;
+    const unsigned nb = blocks_for(n);
+    if (nb > 0)
+        hipLaunchKernelGGL(occupancy_cull_count_kernel, dim3(nb), dim3(OC_BLOCK), 0, s, g, rays, ray_ch, z, n, S, rank, block_counts);
+    if (int rc = launch_compact_scan(block_counts, (int)nb, count, s)) return rc;        // (no blocks: writes the zero count)
+    if (nb > 0)
+        hipLaunchKernelGGL(occupancy_cull_write_kernel, dim3(nb), dim3(OC_BLOCK), 0, s, rays, ray_ch, z, n, S, block_counts, rank, pts_live,
+                           vd_live);
+    return launched();
+}
+
+// ---------------------------------------------------------------------------
+// The inverse of the compaction: one thread per dense row; a culled row is +0.0 in every channel.
+// ---------------------------------------------------------------------------
+template <bool VEC4>
+__global__ __launch_bounds__(OC_BLOCK) void occupancy_expand_kernel(const float *raw_live, const int32_t *rank, int64_t n, int ch, float *raw) {
+    const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx >= n) return;
+    const int r = rank[idx];
+    if constexpr (VEC4) {
+        float4 v = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+        if (r >= 0) v = reinterpret_cast<const float4 *>(raw_live)[r];
+        reinterpret_cast<float4 *>(raw)[idx] = v;
+    } else {
+        const float *src = raw_live + (int64_t)r * ch;
+        float *dst = raw + idx * ch;
+        for (int k = 0; k < ch; ++k) dst[k] = r >= 0 ? src[k] : 0.0f;
+    }
+}
+
+int launch_occupancy_expand(const float *raw_live, const int32_t *rank, int64_t n, int ch, float *raw, hipStream_t s) {
+    if (n <= 0) return NERF_AMD_OK;
+    const bool vec4 = ch == 4 && (reinterpret_cast<uintptr_t>(raw_live) & 15) == 0 && (reinterpret_cast<uintptr_t>(raw) & 15) == 0;
+    if (vec4)
+        hipLaunchKernelGGL(occupancy_expand_kernel<true>, dim3(blocks_for(n)), dim3(OC_BLOCK), 0, s, raw_live, rank, n, ch, raw);
+    else
+        hipLaunchKernelGGL(occupancy_expand_kernel<false>, dim3(blocks_for(n)), dim3(OC_BLOCK), 0, s, raw_live, rank, n, ch, raw);
+    return launched();
+}
+
+}  // namespace na

@@ -7,6 +7,7 @@
 #include <cstdint>
 
 #include "kernels.h"
+#include "mix32.h"
 
 namespace na {
 
@@ -22,11 +23,6 @@ inline int launched() { return hipGetLastError() == hipSuccess ? NERF_AMD_OK : N
 // ---------------------------------------------------------------------------
 // The draw: a keyed bijection of [0, M) evaluated at slots 0..n-1.
 // ---------------------------------------------------------------------------
-__device__ __forceinline__ uint32_t mix32(uint32_t x) {
-    x ^= x >> 16; x *= 0x7feb352du; x ^= x >> 15; x *= 0x846ca68bu; x ^= x >> 16;
-    return x;
-}
-
 // One thread per slot: a four-round Feistel network on 2b bits, walked along its cycle until it lands below M (the walk
 // starts below M, so it returns there), then the pixel of that index and its colour.  The counter is only read here; the
 // one-thread kernel behind this one in the stream advances it, so no block sees a half-advanced value.
@@ -255,6 +251,11 @@ __global__ __launch_bounds__(PS_BLOCK) void compact_write_kernel(const uint8_t *
     for (int w = 0; w < wave; ++w) rank += wave_counts[w];
     list[2 * (int64_t)rank] = (int)(idx % W);
     list[2 * (int64_t)rank + 1] = (int)(idx / W);
+}
+
+int launch_compact_scan(int32_t *block_counts, int n_blocks, int64_t *count, hipStream_t s) {
+    hipLaunchKernelGGL(compact_scan_kernel, dim3(1), dim3(PS_BLOCK), 0, s, block_counts, n_blocks, count);
+    return launched();
 }
 
 int launch_compact_mask(const uint8_t *mask, int H, int W, int32_t *block_counts, int32_t *list, int64_t *count, hipStream_t s) {

@@ -245,6 +245,59 @@ class Renderer(torch.nn.Module):
         # keep the draws alive until the stream has consumed them (caching allocator is stream-ordered)
         return keep
 
+    # ------------------------------------------------------------------ occupancy grid (opt-in)
+    occupancy = None              # a nerf_shared_amd.occupancy.OccupancyGrid: the no-grad render calls evaluate the field at
+                                  # its live points only (nerf_amd_render_rays_culled); None: the dense path, untouched
+    last_cull = None              # with a grid: the points of the last call, summed over its launches, as host ints
+    CULL_GROUP_RAYS = 32768       # rays per culled library call (each call synchronises once per pass)
+
+    def _check_cullable(self, mode):
+        """The culled path is forward-only and noise-free; anything else is refused rather than silently rendered densely."""
+        if mode != "none":
+            raise _lib.NerfAmdError("Renderer.occupancy is set and this call asks for gradients: the occupancy grid culls in the "
+                                    "no-grad render path only.  Render under torch.no_grad() (or with frozen models and rays), or "
+                                    "set renderer.occupancy = None for training and pose estimation")
+        if self.raw_noise_std > 0.:
+            raise _lib.NerfAmdError("Renderer.occupancy is set and raw_noise_std > 0: sigma noise would resurrect culled samples.  "
+                                    "Set raw_noise_std = 0 (as every evaluation render does) or renderer.occupancy = None")
+
+    def _launch_culled(self, rays, coarse_model, fine_model, outs, pytest, stats):
+        """render_rays of one chunk's rays [R, 8|11] through nerf_amd_render_rays_culled into the rows of ``outs``: the
+        chunk's draws are made once, in the reference's order and shapes (as _chunk_io makes them), and the library is
+        called per group of at most CULL_GROUP_RAYS rays on the matching rows.  Adds the four counts to ``stats``."""
+        dev, grid = rays.device, self.occupancy
+        if grid.device != dev:
+            raise _lib.NerfAmdError("Renderer.occupancy is on %s, the rays on %s" % (grid.device, dev))
+        hc, hf, cfg, out_ch = self._handles(dev, coarse_model, fine_model)
+        R, Nc, Ni = rays.shape[0], int(self.N_samples), int(self.N_importance)
+        t_rand, _, _, u, t_lin = self._draws(R, dev, pytest)
+        g = grid._c()
+        counts = (ctypes.c_int64 * 4)()
+        step = self.CULL_GROUP_RAYS
+        ws = _workspace(dev, lib.nerf_amd_render_rays_culled_workspace(cfg, min(R, step), out_ch))
+        for i in range(0, R, step):
+            r = rays[i:i + step]
+            io = _lib.RenderIO()
+            io.rays, io.ray_ch = r.data_ptr(), r.shape[1]
+            io.t_vals = _linspace01(Nc, dev).data_ptr()
+            io.t_rand = None if t_rand is None else t_rand[i:i + step].data_ptr()
+            io.u = None if u is None else u[i:i + step].data_ptr()
+            io.t_lin_imp = _lib.ptr(t_lin)
+            for k in ('rgb_map', 'disp_map', 'acc_map', 'rgb0', 'disp0', 'acc0', 'z_std', 'raw', 'weights', 'z_vals'):
+                v = outs.get(k)
+                setattr(io, k, None if v is None else v[i:i + step].data_ptr())
+            io.workspace, io.workspace_bytes = ws.data_ptr(), ws.numel()
+            with torch.cuda.device(dev):
+                _lib.check(lib.nerf_amd_render_rays_culled(cfg, hc, hf, io, r.shape[0], ctypes.byref(g), counts, _lib.stream_of(dev)),
+                           "nerf_amd_render_rays_culled")
+            for j, k in enumerate(('coarse_live', 'coarse_total', 'fine_live', 'fine_total')):
+                stats[k] += int(counts[j])
+        return (rays, t_rand, u, ws)
+
+    @staticmethod
+    def _new_cull_stats():
+        return {'coarse_live': 0, 'coarse_total': 0, 'fine_live': 0, 'fine_total': 0}
+
     def _launch_batch(self, rays, starts, chunk, coarse_model, fine_model, full):
         """render_batch as ONE library call over whole-batch buffers (nerf_amd_render_batch).  The random draws are made
         per chunk, in the reference's order (t_rand, noise0, u, noise1 of chunk 0, then of chunk 1, ...), into the rows of
@@ -453,6 +506,16 @@ class Renderer(torch.nn.Module):
         if fine_model is not None:
             self._check_model(fine_model, "fine_model")
         mode, deferred = self._grad_mode(coarse_model, fine_model, ray_batch) if rays.shape[0] > 0 else ("none", None)
+        if self.occupancy is not None:
+            self._check_cullable(mode)
+            out_ch = 4 if coarse_model.use_viewdirs else coarse_model.output_ch
+            outs = self._alloc_outputs(rays.shape[0], rays.device, out_ch, retraw, retweights)
+            stats = self._new_cull_stats()
+            self._launch_culled(rays, coarse_model, fine_model, outs, pytest, stats)
+            self.last_cull = stats
+            if retweights and outs['weights'].shape[1] == 1:
+                outs['weights'] = outs['weights'][:, :0]                       # one sample: see raw2outputs
+            return outs
         if mode == "train":
             live = ray_batch.contiguous().float() if (torch.is_grad_enabled() and ray_batch.requires_grad) else rays
             return self._render_rays_train(live, coarse_model, fine_model, retraw, retweights, pytest)
@@ -494,6 +557,15 @@ class Renderer(torch.nn.Module):
         out_ch = 4 if coarse_model.use_viewdirs else coarse_model.output_ch
         starts = list(range(0, N, chunk))
         mode, deferred = self._grad_mode(coarse_model, fine_model, rays_flat) if N > 0 else ("none", None)
+        if self.occupancy is not None:     # per chunk (the reference's draws), the library called per group of <= 32768 rays
+            self._check_cullable(mode)
+            full = self._alloc_outputs(N, dev, out_ch, retraw, False)
+            stats = self._new_cull_stats()
+            for i in starts:
+                part = {k: v[i:i + chunk] for k, v in full.items()}
+                self._launch_culled(rays[i:i + chunk], coarse_model, fine_model, part, False, stats)
+            self.last_cull = stats
+            return full
         if mode == "defer":            # forward-only kernels now, a backward that explains itself later (nerf._grad_request)
             with torch.no_grad():
                 plain = self.render_batch(coarse_model, fine_model, rays_flat, chunk, retraw)
