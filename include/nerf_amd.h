@@ -573,6 +573,38 @@ int nerf_amd_occupancy_cull(const nerf_amd_occupancy_grid *grid, const float *ra
  * rank[i] < 0 (a zero sigma gives alpha 0 and weight 0 in raw2outputs).  One thread per dense row, no memset. */
 int nerf_amd_occupancy_expand(const float *raw_live, const int32_t *rank, int64_t n, int32_t ch, float *raw, void *stream);
 
+/* nerf_amd_occupancy_cull into a list of FIXED capacity (training and pose estimation: no count reaches the host, so the
+ * caller sizes its field launches by `capacity` and the whole step can be captured in a graph).  1 <= capacity < 2^31,
+ * R S < 2^31.  A point is KEPT iff it is live and its stable rank among the live points (point order) is < capacity.
+ *   rank [R S] int32: the row of the point in the compact list, or -1 when culled or over the cap;
+ *   src [capacity] int32: the dense index r S + s of compact row i, or -1 for a padding row;
+ *   pts_live [capacity, 3], vd_live [capacity, 3] (ray_ch == 11, else NULL): kept rows hold the bits
+ *     nerf_amd_occupancy_cull writes; the PADDING rows [kept, capacity) hold the point float32((lo_a + hi_a) / 2) per axis
+ *     (the box centre, formed in double on the host and rounded once) and the view direction (0, 0, 1) -- a fixed finite
+ *     point, so the field is finite there and a zero dL/draw row contributes 0 * finite = 0 to every gradient;
+ *   counts int64 DEVICE [2] = {live, kept = min(live, capacity)}, overwritten.
+ * Count -> scan -> write like nerf_amd_occupancy_cull; the write launch covers max(R S, capacity) threads, so the padding
+ * rows need no host value.  R == 0 writes counts {0, 0} and a list that is all padding (rays, z, rank, block_counts may
+ * then be NULL).  block_counts: (R S + 255) / 256 int32 of DEVICE scratch. */
+int nerf_amd_occupancy_cull_capped(const nerf_amd_occupancy_grid *grid, const float *rays, int32_t ray_ch, const float *z, int64_t R,
+                                   int32_t S, int64_t capacity, int32_t *block_counts, int32_t *rank, int32_t *src, float *pts_live,
+                                   float *vd_live, int64_t *counts, void *stream);
+
+/* The backward of nerf_amd_occupancy_expand: dense [n, ch], src [capacity] -> live [capacity, ch]: row i = dense[src[i]], or
+ * +0.0 in every channel where src[i] < 0.  One thread per compact row. */
+int nerf_amd_occupancy_gather_rows(const float *dense, const int32_t *src, int64_t capacity, int32_t ch, float *live, void *stream);
+
+/* The backward of "pts = o + d z at the kept samples" (and of "view direction of the kept samples") onto the ray batch:
+ * rank [R S] and z [R, S] as above, g_pts_live [capacity, 3], g_vd_live [capacity, 3] or NULL -> g_rays [R, ray_ch],
+ * overwritten.  Per ray, summed over its KEPT samples (rank >= 0) only:
+ *   columns 0..2 = sum_s g_pts;   columns 3..5 = sum_s (g_pts * z), each product rounded before it is added;
+ *   columns 6, 7 = 0;   columns 8..10 (ray_ch == 11) = sum_s g_vd (0 when g_vd_live is NULL).
+ * Summation order, per column, in fp32: 64 partial sums start at +0.0; partial l adds the terms of the kept samples
+ * s = l, l + 64, l + 128, ... in ascending order; then for m = 32, 16, 8, 4, 2, 1 in turn every partial becomes
+ * v_l = v_l + v_(l xor m) (all 64 at once), and the result is partial 0.  One 64-lane wave per ray, no atomics. */
+int nerf_amd_occupancy_ray_grads(const int32_t *rank, const float *z, const float *g_pts_live, const float *g_vd_live, int64_t R,
+                                 int32_t S, int32_t ray_ch, float *g_rays, void *stream);
+
 /* The field at a point list: pts [n,3], viewdirs [n,3] (one per POINT; NULL for a model without view branch) -> raw [n,ch].
  * Unlike nerf_amd_nerf_forward it takes the RENDER path's choice of weight stream (tuning key 2: the folded stream of a
  * bf16 view-branch model when NERF_AMD_COPY_BF16_FOLD is current), so a compacted pass runs the kernel the dense pass

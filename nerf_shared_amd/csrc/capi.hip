@@ -940,6 +940,7 @@ int occ_grid(const nerf_amd_occupancy_grid *g, bool need_words, OccGrid *out) {
         out->n[a] = g->n[a];
         out->scale[a] = (float)((double)g->n[a] / (hi - lo));
         out->width[a] = (float)((hi - lo) / (double)g->n[a]);
+        out->centre[a] = (float)((lo + hi) / 2.0);
         if (!std::isfinite(out->scale[a]) || !(out->width[a] > 0.0f)) return fail(NERF_AMD_EINVAL, "occupancy grid: box too thin or too wide for fp32");
     }
     return NERF_AMD_OK;
@@ -1065,6 +1066,35 @@ int nerf_amd_occupancy_expand(const float *raw_live, const int32_t *rank, int64_
     if (n < 0 || ch < 1 || (n > 0 && (!rank || !raw))) return fail(NERF_AMD_EINVAL, "bad occupancy_expand arguments");
     int rc = launch_occupancy_expand(raw_live, rank, n, ch, raw, static_cast<hipStream_t>(stream));
     return rc ? fail(rc, "occupancy_expand launch failed") : NERF_AMD_OK;
+}
+
+int nerf_amd_occupancy_cull_capped(const nerf_amd_occupancy_grid *grid, const float *rays, int32_t ray_ch, const float *z, int64_t R,
+                                   int32_t S, int64_t capacity, int32_t *block_counts, int32_t *rank, int32_t *src, float *pts_live,
+                                   float *vd_live, int64_t *counts, void *stream) {
+    OccGrid g;
+    if (int rc = occ_grid(grid, true, &g)) return rc;
+    if (R < 0 || S < 1 || (ray_ch != 8 && ray_ch != 11) || R * (int64_t)S >= ((int64_t)1 << 31) || capacity < 1 ||
+        capacity >= ((int64_t)1 << 31) || !counts || !src || !pts_live || (R > 0 && (!rays || !z || !block_counts || !rank)) ||
+        (vd_live && ray_ch != 11))
+        return fail(NERF_AMD_EINVAL, "bad occupancy_cull_capped arguments");
+    int rc = launch_occupancy_cull_capped(g, rays, ray_ch, z, R, S, capacity, block_counts, rank, src, pts_live, vd_live, counts,
+                                          static_cast<hipStream_t>(stream));
+    return rc ? fail(rc, "occupancy_cull_capped launch failed") : NERF_AMD_OK;
+}
+
+int nerf_amd_occupancy_gather_rows(const float *dense, const int32_t *src, int64_t capacity, int32_t ch, float *live, void *stream) {
+    if (capacity < 0 || ch < 1 || (capacity > 0 && (!dense || !src || !live))) return fail(NERF_AMD_EINVAL, "bad occupancy_gather_rows arguments");
+    int rc = launch_occupancy_gather_rows(dense, src, capacity, ch, live, static_cast<hipStream_t>(stream));
+    return rc ? fail(rc, "occupancy_gather_rows launch failed") : NERF_AMD_OK;
+}
+
+int nerf_amd_occupancy_ray_grads(const int32_t *rank, const float *z, const float *g_pts_live, const float *g_vd_live, int64_t R,
+                                 int32_t S, int32_t ray_ch, float *g_rays, void *stream) {
+    if (R < 0 || S < 1 || (ray_ch != 8 && ray_ch != 11) || R * (int64_t)S >= ((int64_t)1 << 31) ||
+        (R > 0 && (!rank || !z || !g_pts_live || !g_rays)) || (g_vd_live && ray_ch != 11))
+        return fail(NERF_AMD_EINVAL, "bad occupancy_ray_grads arguments");
+    int rc = launch_occupancy_ray_grads(rank, z, g_pts_live, g_vd_live, R, S, ray_ch, g_rays, static_cast<hipStream_t>(stream));
+    return rc ? fail(rc, "occupancy_ray_grads launch failed") : NERF_AMD_OK;
 }
 
 int nerf_amd_field_points(const nerf_amd_model *m, const float *pts, const float *viewdirs, int64_t n, float *raw,

@@ -225,6 +225,7 @@ struct OccGrid {
     float lo[3], scale[3], width[3];   // scale = float32(n / (hi - lo)), width = float32((hi - lo) / n), each rounded once from double
     int32_t n[3];
     int32_t outside_live;
+    float centre[3];                   // float32((lo + hi) / 2), rounded once from double: the point of a padding row (cull_capped)
 };
 int launch_occupancy_query(const OccGrid &g, const float *pts, int64_t n, uint8_t *live, int32_t *cell, hipStream_t s);
 int launch_occupancy_sample_points(const OccGrid &g, int64_t c0, int64_t c1, int K, uint32_t seed, float *pts, hipStream_t s);
@@ -234,5 +235,12 @@ int launch_occupancy_dilate(const int32_t *in, int nx, int ny, int nz, int reach
 int launch_occupancy_cull(const OccGrid &g, const float *rays, int ray_ch, const float *z, int64_t R, int S, int32_t *block_counts,
                           int32_t *rank, float *pts_live, float *vd_live, int64_t *count, hipStream_t s);
 int launch_occupancy_expand(const float *raw_live, const int32_t *rank, int64_t n, int ch, float *raw, hipStream_t s);
+// the capped compaction of training and pose estimation, the backward of expand, and the backward of the kept points onto the rays
+int launch_occupancy_cull_capped(const OccGrid &g, const float *rays, int ray_ch, const float *z, int64_t R, int S, int64_t capacity,
+                                 int32_t *block_counts, int32_t *rank, int32_t *src, float *pts_live, float *vd_live, int64_t *counts,
+                                 hipStream_t s);
+int launch_occupancy_gather_rows(const float *dense, const int32_t *src, int64_t capacity, int ch, float *live, hipStream_t s);
+int launch_occupancy_ray_grads(const int32_t *rank, const float *z, const float *g_pts, const float *g_vd, int64_t R, int S, int ray_ch,
+                               float *g_rays, hipStream_t s);
 
 }  // namespace na

@@ -223,6 +223,70 @@ int launch_occupancy_cull(const OccGrid &g, const float *rays, int ray_ch, const
 }
 
 // ---------------------------------------------------------------------------
+// The compaction with a cap (training and pose estimation: a list of fixed capacity, so no count ever reaches the host).
+// The count and scan launches are the uncapped ones; the write launch covers max(n, capacity) threads: a live point whose
+// rank is below the cap writes its row and src[rank], every other point gets rank -1, and thread i < capacity writes
+// padding row i when i >= kept = min(live, capacity).  A row is written by exactly one thread: below `kept` by the live
+// point of that rank, from `kept` on by thread i.
+// ---------------------------------------------------------------------------
+__global__ __launch_bounds__(OC_BLOCK) void occupancy_cull_capped_write_kernel(OccGrid g, const float *rays, int ray_ch, const float *z,
+                                                                               int64_t n, int S, int64_t capacity,
+                                                                               const int32_t *block_offsets, int32_t *rank, int32_t *src,
+                                                                               float *pts_live, float *vd_live, int64_t *counts) {
+    __shared__ int wave_counts[OC_BLOCK / 64];
+    const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const bool on = idx < n && rank[idx] == 0;
+    const uint64_t ballot = __ballot(on);
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    if (lane == 0) wave_counts[wave] = __popcll(ballot);
+    __syncthreads();
+    const int64_t live = counts[0];                                   // (the scan's total; this launch only reads it)
+    const int64_t kept = live < capacity ? live : capacity;
+    if (idx == 0) counts[1] = kept;
+    if (idx < capacity && idx >= kept) {
+        src[idx] = -1;
+        float *dst = pts_live + 3 * idx;
+        dst[0] = g.centre[0]; dst[1] = g.centre[1]; dst[2] = g.centre[2];
+        if (vd_live) {
+            float *dv = vd_live + 3 * idx;
+            dv[0] = 0.0f; dv[1] = 0.0f; dv[2] = 1.0f;
+        }
+    }
+    if (!on) return;
+    int r = block_offsets[blockIdx.x] + __popcll(ballot & (((uint64_t)1 << lane) - 1));
+    for (int w = 0; w < wave; ++w) r += wave_counts[w];
+    if (r >= capacity) {
+        rank[idx] = -1;
+        return;
+    }
+    rank[idx] = r;
+    src[r] = (int32_t)idx;
+    float p[3];
+    int64_t ray;
+    sample_point(rays, ray_ch, z, idx, S, p, &ray);
+    float *dst = pts_live + 3 * (int64_t)r;
+    dst[0] = p[0]; dst[1] = p[1]; dst[2] = p[2];
+    if (vd_live) {
+        const float *v = rays + ray * ray_ch + 8;
+        float *dv = vd_live + 3 * (int64_t)r;
+        dv[0] = v[0]; dv[1] = v[1]; dv[2] = v[2];
+    }
+}
+
+int launch_occupancy_cull_capped(const OccGrid &g, const float *rays, int ray_ch, const float *z, int64_t R, int S, int64_t capacity,
+                                 int32_t *block_counts, int32_t *rank, int32_t *src, float *pts_live, float *vd_live, int64_t *counts,
+                                 hipStream_t s) {
+    const int64_t n = R * S;
+    const unsigned nb = blocks_for(n);
+    if (nb > 0)
+        hipLaunchKernelGGL(occupancy_cull_count_kernel, dim3(nb), dim3(OC_BLOCK), 0, s, g, rays, ray_ch, z, n, S, rank, block_counts);
+    if (int rc = launch_compact_scan(block_counts, (int)nb, counts, s)) return rc;       // (no blocks: writes the zero count)
+    hipLaunchKernelGGL(occupancy_cull_capped_write_kernel, dim3(blocks_for(n > capacity ? n : capacity)), dim3(OC_BLOCK), 0, s, g, rays,
+                       ray_ch, z, n, S, capacity, block_counts, rank, src, pts_live, vd_live, counts);
+    return launched();
+}
+
+// ---------------------------------------------------------------------------
 // The inverse of the compaction: one thread per dense row; a culled row is +0.0 in every channel.
 // ---------------------------------------------------------------------------
 template <bool VEC4>
@@ -248,6 +312,86 @@ int launch_occupancy_expand(const float *raw_live, const int32_t *rank, int64_t 
         hipLaunchKernelGGL(occupancy_expand_kernel<true>, dim3(blocks_for(n)), dim3(OC_BLOCK), 0, s, raw_live, rank, n, ch, raw);
     else
         hipLaunchKernelGGL(occupancy_expand_kernel<false>, dim3(blocks_for(n)), dim3(OC_BLOCK), 0, s, raw_live, rank, n, ch, raw);
+    return launched();
+}
+
+// ---------------------------------------------------------------------------
+// The backward of the expansion: one thread per compact row; a padding row (src < 0) is +0.0 in every channel.
+// ---------------------------------------------------------------------------
+template <bool VEC4>
+__global__ __launch_bounds__(OC_BLOCK) void occupancy_gather_rows_kernel(const float *dense, const int32_t *src, int64_t capacity, int ch,
+                                                                         float *live) {
+    const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx >= capacity) return;
+    const int r = src[idx];
+    if constexpr (VEC4) {
+        float4 v = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+        if (r >= 0) v = reinterpret_cast<const float4 *>(dense)[r];
+        reinterpret_cast<float4 *>(live)[idx] = v;
+    } else {
+        const float *from = dense + (int64_t)r * ch;
+        float *dst = live + idx * ch;
+        for (int k = 0; k < ch; ++k) dst[k] = r >= 0 ? from[k] : 0.0f;
+    }
+}
+
+int launch_occupancy_gather_rows(const float *dense, const int32_t *src, int64_t capacity, int ch, float *live, hipStream_t s) {
+    if (capacity <= 0) return NERF_AMD_OK;
+    const bool vec4 = ch == 4 && (reinterpret_cast<uintptr_t>(dense) & 15) == 0 && (reinterpret_cast<uintptr_t>(live) & 15) == 0;
+    if (vec4)
+        hipLaunchKernelGGL(occupancy_gather_rows_kernel<true>, dim3(blocks_for(capacity)), dim3(OC_BLOCK), 0, s, dense, src, capacity, ch, live);
+    else
+        hipLaunchKernelGGL(occupancy_gather_rows_kernel<false>, dim3(blocks_for(capacity)), dim3(OC_BLOCK), 0, s, dense, src, capacity, ch, live);
+    return launched();
+}
+
+// ---------------------------------------------------------------------------
+// The backward of "pts = o + d z at the kept samples" onto the ray batch: one 64-lane wave per ray (four rays per block).
+// Lane l adds the kept samples s = l, l + 64, ... in ascending order into accumulators that start at +0.0, then the
+// butterfly v_l = v_l + v_(l xor m) for m = 32, 16, 8, 4, 2, 1 (fp32 addition commutes, so every lane ends with the same
+// bits); lane 0 stores.  No atomics: the order is the header's, and a numpy mirror reproduces it.
+// ---------------------------------------------------------------------------
+__global__ __launch_bounds__(OC_BLOCK) void occupancy_ray_grads_kernel(const int32_t *rank, const float *z, const float *g_pts,
+                                                                       const float *g_vd, int64_t R, int S, int ray_ch, float *g_rays) {
+    const int lane = threadIdx.x & 63;
+    const int64_t ray = (int64_t)blockIdx.x * (OC_BLOCK / 64) + (threadIdx.x >> 6);
+    if (ray >= R) return;                                             // (whole waves leave: the shuffles below see all 64 lanes)
+    float acc[9] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
+    for (int s = lane; s < S; s += 64) {
+        const int64_t idx = ray * S + s;
+        const int r = rank[idx];
+        if (r < 0) continue;
+        const float zz = z[idx];
+        const float *gp = g_pts + 3 * (int64_t)r;
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            const float v = gp[k];
+            const float vz = v * zz;                                  // rounded before it is added (-ffp-contract=off)
+            acc[k] = acc[k] + v;
+            acc[3 + k] = acc[3 + k] + vz;
+        }
+        if (g_vd) {
+            const float *gv = g_vd + 3 * (int64_t)r;
+#pragma unroll
+            for (int k = 0; k < 3; ++k) acc[6 + k] = acc[6 + k] + gv[k];
+        }
+    }
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1)
+#pragma unroll
+        for (int k = 0; k < 9; ++k) acc[k] = acc[k] + __shfl_xor(acc[k], m, 64);
+    if (lane != 0) return;
+    float *out = g_rays + ray * ray_ch;
+#pragma unroll
+    for (int k = 0; k < 6; ++k) out[k] = acc[k];
+    out[6] = 0.0f; out[7] = 0.0f;
+    if (ray_ch == 11) { out[8] = acc[6]; out[9] = acc[7]; out[10] = acc[8]; }
+}
+
+int launch_occupancy_ray_grads(const int32_t *rank, const float *z, const float *g_pts, const float *g_vd, int64_t R, int S, int ray_ch,
+                               float *g_rays, hipStream_t s) {
+    if (R <= 0) return NERF_AMD_OK;
+    hipLaunchKernelGGL(occupancy_ray_grads_kernel, dim3(blocks_for(R * 64)), dim3(OC_BLOCK), 0, s, rank, z, g_pts, g_vd, R, S, ray_ch, g_rays);
     return launched();
 }
 

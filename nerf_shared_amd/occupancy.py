@@ -7,9 +7,14 @@ NDC coordinates).  It is filled once from the trained models' density and then s
     grid.fill_from_density([coarse_model, fine_model])
     renderer.occupancy = grid
 
+That culls the no-grad render calls.  Training and pose estimation cull through a TrainCull on the same grid
+(renderer.train_occupancy = TrainCull(grid)): compact lists of fixed capacity, nothing synchronises, the step still captures;
+OccupancyGrid.refresh_from_density keeps the grid following the models in place.
+
 Every operation is a HIP kernel of csrc/occupancy.hip with an exactly defined result; there is no CPU path.
 """
 import ctypes
+import math
 
 import numpy as np
 import torch
@@ -52,6 +57,7 @@ class OccupancyGrid:
             raise _lib.NerfAmdError("an OccupancyGrid lives on a ROCm (cuda) device, not on %s -- there is no CPU path" % dev)
         self.device = dev
         self._words = None           # made on first use, so building a grid touches no device
+        self._raw_words = None       # the undilated plane of refresh_from_density, made on its first use
 
     @property
     def words(self):
@@ -66,6 +72,15 @@ class OccupancyGrid:
     @words.setter
     def words(self, w):
         self._words = w
+        self._raw_words = None       # whoever replaces the grid's bits (dilate, a caller) starts refresh_from_density over
+
+    @property
+    def raw_words(self):
+        """The undilated plane refresh_from_density marks into: what fill_from_density marked before it dilated, or, for a
+        grid that was set another way (set_mask, a caller's words), a copy of `words` made on first use."""
+        if self._raw_words is None:
+            self._raw_words = self.words.clone()
+        return self._raw_words
 
     # ------------------------------------------------------------------ plumbing
     def _c(self, words=True):
@@ -133,6 +148,7 @@ class OccupancyGrid:
         bits[:self.n_cells] = mask.reshape(-1).to(torch.int64)
         w = (bits.reshape(-1, 32) << torch.arange(32, dtype=torch.int64, device=self.device)[None, :]).sum(1)
         self.words.copy_(torch.where(w >= 2 ** 31, w - 2 ** 32, w).to(torch.int32))
+        self._raw_words = None
 
     def occupied_fraction(self):
         """Share of live cells.  SYNCHRONISES (the count comes to the host)."""
@@ -154,27 +170,232 @@ class OccupancyGrid:
         dilation.  threshold 0 is the relu cut: a sample with raw sigma <= 0 contributes exactly nothing to a render.
         Each model is evaluated with model.get_density, in its own precision, on the current stream, a chunk of cells at a
         time (one chunk of temporaries alive at a time); nothing synchronises."""
+        self._mark_cells("fill_from_density", models, 0, self.n_cells, threshold, samples_per_cell, seed, "words")
+        self._raw_words = None
+        if dilate:
+            marked = self._words             # dilate() binds a new tensor to `words`: this one stays the undilated plane, so
+            self.dilate(dilate)              # that a later refresh_from_density dilates what was marked, not what was
+            self._raw_words = marked         # already dilated
+        return self
+
+    def _mark_cells(self, who, models, lo, hi, threshold, samples_per_cell, seed, words):
+        """Sets the bits of the cells [lo, hi) of the plane named `words` ('words' / 'raw_words'; lo a multiple of 32) from the
+        models' density, a chunk of cells at a time."""
         if not isinstance(models, (list, tuple)):
             models = [models]
         models = [m for m in models if m is not None]
         if not models:
-            raise ValueError("fill_from_density needs at least one model")
+            raise ValueError("%s needs at least one model" % who)
         K = int(samples_per_cell)
         if K < 1:
             raise ValueError("samples_per_cell must be >= 1")
         cells = max(32, (FILL_CHUNK_POINTS // K) // 32 * 32)
-        buf = torch.empty(min(cells, (self.n_cells + 31) // 32 * 32) * K, 3, dtype=torch.float32, device=self.device)
+        buf = torch.empty(min(cells, (hi - lo + 31) // 32 * 32) * K, 3, dtype=torch.float32, device=self.device)
         stream = _lib.stream_of(self.device)
+        words = getattr(self, words)
         with torch.no_grad():
-            for c0 in range(0, self.n_cells, cells):
-                c1 = min(c0 + cells, self.n_cells)
+            for c0 in range(lo, hi, cells):
+                c1 = min(c0 + cells, hi)
                 pts = self.sample_points(c0, c1, K, seed, out=buf)
                 for i, m in enumerate(models):
                     sigma = m.get_density(pts).contiguous()
                     with torch.cuda.device(self.device):
                         _lib.check(lib.nerf_amd_occupancy_mark(sigma.data_ptr(), c0, c1, K, float(threshold), int(i > 0),
-                                                               self.words.data_ptr(), stream), "nerf_amd_occupancy_mark")
+                                                               words.data_ptr(), stream), "nerf_amd_occupancy_mark")
                     del sigma
-        if dilate:
-            self.dilate(dilate)
+
+    def refresh_from_density(self, models, cells=None, threshold=0.0, samples_per_cell=4, dilate=1, seed=0):
+        """Follow the models while they train: re-mark the cells [c0, c1) = `cells` (default: every cell) as fill_from_density
+        marks them, into the separate undilated plane `raw_words` (fill_from_density's marks before its dilation; for a grid
+        set another way a copy of `words` made on first use -- use the `dilate` the grid was filled with), then dilate
+        `raw_words` INTO the existing `words` storage.  `words` is never rebound -- a captured step has baked
+        words.data_ptr(), and reads the grid's bits at replay -- and nothing synchronises: every launch is enqueued on the
+        current stream, so call it between replays on the stream that replays.  c0 must be a multiple of 32 and c1 a
+        multiple of 32 or the number of cells (a marking thread owns whole words).  A rotating slab with a changing seed is
+        the caller's loop -- "every k steps refresh 1/m of the cells"::
+
+            if step % k == 0:
+                i = (step // k) % m
+                grid.refresh_from_density(models, cells=grid.slab(i, m), seed=step)
+        """
+        c0, c1 = (0, self.n_cells) if cells is None else (int(cells[0]), int(cells[1]))
+        if not (0 <= c0 <= c1 <= self.n_cells) or c0 % 32 or (c1 % 32 and c1 != self.n_cells):
+            raise ValueError("cells must be (c0, c1) with 0 <= c0 <= c1 <= %d, c0 a multiple of 32 and c1 a multiple of 32 or "
+                             "the number of cells (got %r)" % (self.n_cells, cells))
+        self._mark_cells("refresh_from_density", models, c0, c1, threshold, samples_per_cell, seed, "raw_words")
+        raw = self.raw_words
+        with torch.cuda.device(self.device):
+            _lib.check(lib.nerf_amd_occupancy_dilate(raw.data_ptr(), self.resolution[0], self.resolution[1], self.resolution[2],
+                                                     int(dilate), self._words.data_ptr(), _lib.stream_of(self.device)),
+                       "nerf_amd_occupancy_dilate")
         return self
+
+    def slab(self, i, m):
+        """The i-th (mod m) of m contiguous cell ranges that cover the grid, each starting at a multiple of 32."""
+        per = (self.n_words + m - 1) // m * 32
+        c0 = min((i % m) * per, self.n_cells)
+        return c0, min(c0 + per, self.n_cells)
+
+
+def _capacity(fraction, n):
+    """C = min(n, max(1, ceil(fraction n)))."""
+    return min(n, max(1, int(math.ceil(fraction * n)))) if n > 0 else 1
+
+
+class TrainCull:
+    """The occupancy grid in training and pose estimation (set it as Renderer.train_occupancy): every pass of a "train"
+    call compacts its live sample points into a list of FIXED capacity C = min(R S, max(1, ceil(fraction R S))), the
+    training kernels run on that list in their explicit-points mode (R = C, S = 1), and nothing synchronises, so the step
+    can be captured (utils.CapturedTrainStep and the pose steps capture whatever the renderer does: the fractions are
+    frozen at capture, the grid's bits are read at replay).  Rows past the live count are padding (the box centre, a zero
+    dL/draw row); live points past the cap OVERFLOW: they are treated as empty -- raw = +0.0, no gradient -- which is a
+    defined result, visible in stats(), never an error.
+
+    The caller drives the calibration: a few eager steps at fraction 1.0 (no saving, but the counts are exact), then
+    calibrate(), then capture::
+
+        cull = occupancy.TrainCull(grid)
+        renderer.train_occupancy = cull
+        for _ in range(8): eager_step()
+        cull.calibrate(margin=1.25)
+        step = utils.CapturedTrainStep(...)
+        cull.stats(reset=True)            # the warm-up steps of the construction counted too
+
+    Keep the eager steps in a function of their own: a render result that outlives them keeps an autograd graph over the
+    parameters alive into the capture (utils.CapturedTrainStep).
+    """
+
+    PASSES = ("coarse", "fine")
+
+    def __init__(self, grid, coarse_fraction=1.0, fine_fraction=1.0):
+        if not isinstance(grid, OccupancyGrid):
+            raise TypeError("grid must be an OccupancyGrid (got %s)" % type(grid).__name__)
+        self.grid = grid
+        self.coarse_fraction = self._fraction(coarse_fraction, "coarse_fraction")
+        self.fine_fraction = self._fraction(fine_fraction, "fine_fraction")
+        self._totals = None          # int64 [2, 3] on the grid's device: {live, kept, total} per pass; made on first use
+
+    @staticmethod
+    def _fraction(v, name):
+        try:
+            f = float(v)
+        except (TypeError, ValueError):
+            f = float("nan")
+        if not (0.0 < f <= 1.0):
+            raise ValueError("%s must be in (0, 1] (got %r)" % (name, v))
+        return f
+
+    def capacity(self, fine_pass, n_points):
+        return _capacity(self.fine_fraction if fine_pass else self.coarse_fraction, int(n_points))
+
+    @property
+    def totals(self):
+        if self._totals is None:
+            self._totals = torch.zeros(2, 3, dtype=torch.int64, device=self.grid.device)
+        return self._totals
+
+    def cull(self, rays, z, fine_pass):
+        """rays [R, 8|11], z [R, S] (fp32, contiguous, on the grid's device) -> (pts_live [C, 3], vd_live [C, 3] | None, rank
+        [R S], src [C]); differentiable with respect to the rays.  Adds the pass's counts to the running totals (a torch add
+        on the current stream: it captures)."""
+        if rays.device != self.grid.device:
+            raise _lib.NerfAmdError("Renderer.train_occupancy is on %s, the rays on %s" % (self.grid.device, rays.device))
+        return _CullFn.apply(rays, z, self, bool(fine_pass))
+
+    def stats(self, reset=False):
+        """{'coarse': {live, kept, total, overflow}, 'fine': {...}} since the last reset, overflow = live - kept.
+        SYNCHRONISES: the totals come to the host."""
+        t = self.totals.cpu().tolist()
+        if reset:
+            self.totals.zero_()
+        return {name: dict(live=row[0], kept=row[1], total=row[2], overflow=row[0] - row[1]) for name, row in zip(self.PASSES, t)}
+
+    def calibrate(self, margin=1.25):
+        """Set each pass's fraction to min(1, margin live / total) from the totals gathered so far (a pass that has not run
+        keeps its fraction) and reset them.  SYNCHRONISES (stats).  Returns the two fractions."""
+        if not margin >= 1.0:
+            raise ValueError("margin must be >= 1 (got %r)" % (margin,))
+        s = self.stats(reset=True)
+        for name in self.PASSES:
+            if s[name]["total"] > 0:
+                f = min(1.0, margin * s[name]["live"] / s[name]["total"])
+                setattr(self, name + "_fraction", f if f > 0.0 else 1.0 / s[name]["total"])
+        return self.coarse_fraction, self.fine_fraction
+
+
+class _CullFn(torch.autograd.Function):
+    """nerf_amd_occupancy_cull_capped; the backward (it runs only when the rays require a gradient) is
+    nerf_amd_occupancy_ray_grads."""
+
+    @staticmethod
+    def forward(ctx, rays, z, cull, fine_pass):
+        grid, dev = cull.grid, rays.device
+        R, S = z.shape
+        n = R * S
+        C = cull.capacity(fine_pass, n)
+        has_vd = rays.shape[1] == 11
+        f = dict(device=dev, dtype=torch.float32)
+        i32 = dict(device=dev, dtype=torch.int32)
+        rank, src = torch.empty(n, **i32), torch.empty(C, **i32)
+        block_counts = torch.empty((n + 255) // 256, **i32)
+        pts, vd = torch.empty(C, 3, **f), (torch.empty(C, 3, **f) if has_vd else None)
+        counts = torch.empty(2, dtype=torch.int64, device=dev)
+        g = grid._c()
+        with torch.cuda.device(dev):
+            _lib.check(lib.nerf_amd_occupancy_cull_capped(ctypes.byref(g), rays.data_ptr(), rays.shape[1], z.data_ptr(), R, S, C,
+                                                          block_counts.data_ptr(), rank.data_ptr(), src.data_ptr(), pts.data_ptr(),
+                                                          _lib.ptr(vd), counts.data_ptr(), _lib.stream_of(dev)),
+                       "nerf_amd_occupancy_cull_capped")
+        row = cull.totals[1 if fine_pass else 0]
+        row[:2].add_(counts)
+        row[2].add_(n)
+        ctx.save_for_backward(rank, z)
+        ctx.ray_ch = rays.shape[1]
+        ctx.mark_non_differentiable(rank, src)
+        ctx.set_materialize_grads(False)
+        return pts, vd, rank, src
+
+    @staticmethod
+    def backward(ctx, g_pts, g_vd, _g_rank, _g_src):
+        if g_pts is None and g_vd is None:
+            return None, None, None, None
+        rank, z = ctx.saved_tensors
+        R, S = z.shape
+        dev = z.device
+        if g_pts is None:
+            g_pts = torch.zeros(g_vd.shape[0], 3, device=dev, dtype=torch.float32)
+        g_pts = g_pts.contiguous().float()
+        g_vd = None if g_vd is None else g_vd.contiguous().float()
+        g_rays = torch.empty(R, ctx.ray_ch, device=dev, dtype=torch.float32)
+        with torch.cuda.device(dev):
+            _lib.check(lib.nerf_amd_occupancy_ray_grads(rank.data_ptr(), z.data_ptr(), g_pts.data_ptr(), _lib.ptr(g_vd), R, S, ctx.ray_ch,
+                                                        g_rays.data_ptr(), _lib.stream_of(dev)), "nerf_amd_occupancy_ray_grads")
+        return g_rays, None, None, None
+
+
+class _ExpandFn(torch.autograd.Function):
+    """raw_live [C, ch] -> raw [n, ch] (nerf_amd_occupancy_expand: +0.0 where rank < 0); the backward is
+    nerf_amd_occupancy_gather_rows (+0.0 in the padding rows)."""
+
+    @staticmethod
+    def forward(ctx, raw_live, rank, src):
+        raw_live = raw_live.contiguous()
+        n, ch, dev = rank.shape[0], raw_live.shape[1], raw_live.device
+        raw = torch.empty(n, ch, device=dev, dtype=torch.float32)
+        with torch.cuda.device(dev):
+            _lib.check(lib.nerf_amd_occupancy_expand(raw_live.data_ptr(), rank.data_ptr(), n, ch, raw.data_ptr(), _lib.stream_of(dev)),
+                       "nerf_amd_occupancy_expand")
+        ctx.save_for_backward(src)
+        ctx.ch = ch
+        return raw
+
+    @staticmethod
+    def backward(ctx, g_raw):
+        src, = ctx.saved_tensors
+        g = g_raw.contiguous().float()
+        dev = g.device
+        g_live = torch.empty(src.shape[0], ctx.ch, device=dev, dtype=torch.float32)
+        with torch.cuda.device(dev):
+            _lib.check(lib.nerf_amd_occupancy_gather_rows(g.data_ptr(), src.data_ptr(), src.shape[0], ctx.ch, g_live.data_ptr(),
+                                                          _lib.stream_of(dev)), "nerf_amd_occupancy_gather_rows")
+        return g_live, None, None

@@ -298,6 +298,36 @@ class Renderer(torch.nn.Module):
     def _new_cull_stats():
         return {'coarse_live': 0, 'coarse_total': 0, 'fine_live': 0, 'fine_total': 0}
 
+    # ------------------------------------------------------------------ occupancy grid in training and pose estimation (opt-in)
+    train_occupancy = None        # a nerf_shared_amd.occupancy.TrainCull: a call in "train" mode (parameters or rays ask for
+                                  # gradients, the training kernels cover the models) evaluates each field at a compact list
+                                  # of fixed capacity; nothing synchronises, so a captured step captures it.  None: the dense
+                                  # training path, launch for launch.  A no-grad call ignores it (that is `occupancy`).
+
+    def _field_culled(self, cull, net, rays, z, fine_pass):
+        """raw [R, S, ch] of one pass with the field evaluated at the kept points only: capped cull -> the training kernels in
+        their explicit-points mode on the compact list (R = C, S = 1; a model that asks for no gradient keeps its forward-only
+        kernel, nerf_amd_field_points, on the same list) -> expand.  Culled and overflowing samples have raw = +0.0."""
+        from . import occupancy as occ
+        R, S = z.shape
+        dev = rays.device
+        if net.use_viewdirs and rays.shape[1] != 11:
+            raise _lib.NerfAmdError("a model with a view branch needs rays [N, 11], got %s" % (tuple(rays.shape),))
+        pts, vd, rank, src = cull.cull(rays, z, fine_pass)
+        if not net.use_viewdirs:
+            vd = None
+        C = pts.shape[0]
+        if net._grad_request(dev, rays)[0] == "train":
+            raw_live = nerf_mod._train_field(net, net._train_precision(), pts, vd, None, None, C, 1)
+        else:
+            with torch.no_grad():
+                handle = net._model_handle(dev)
+                raw_live = torch.empty(C, 4 if net.use_viewdirs else net.output_ch, device=dev, dtype=torch.float32)
+                with torch.cuda.device(dev):
+                    _lib.check(lib.nerf_amd_field_points(handle, pts.data_ptr(), _lib.ptr(vd), C, raw_live.data_ptr(),
+                                                         net._precision_code(), _lib.stream_of(dev)), "nerf_amd_field_points")
+        return occ._ExpandFn.apply(raw_live, rank, src).reshape(R, S, raw_live.shape[1])
+
     def _launch_batch(self, rays, starts, chunk, coarse_model, fine_model, full):
         """render_batch as ONE library call over whole-batch buffers (nerf_amd_render_batch).  The random draws are made
         per chunk, in the reference's order (t_rand, noise0, u, noise1 of chunk 0, then of chunk 1, ...), into the rows of
@@ -428,14 +458,23 @@ class Renderer(torch.nn.Module):
                        "nerf_amd_coarse_z")
         rays_d = rays[:, 3:6]            # a view: composite gradients with respect to |d| flow back into `rays`
 
+        cull = self.train_occupancy
+        if cull is not None and self.raw_noise_std > 0.:
+            raise _lib.NerfAmdError("Renderer.train_occupancy is set and raw_noise_std > 0: sigma noise would resurrect culled samples.  "
+                                    "Set raw_noise_std = 0 or renderer.train_occupancy = None")
+
         def field(net, zz):
             # a model that asks for no gradient (frozen, and the rays carry none) keeps its own forward-only kernel and
             # precision; only models that train go through the training kernels
+            if cull is not None:
+                return self._field_culled(cull, net, rays, zz, zz is not z_c)
             if net._grad_request(dev, rays)[0] == "train":
                 return net.forward_rays(rays, zz)
             with torch.no_grad():
                 pts = rays[:, None, 0:3] + rays[:, None, 3:6] * zz[:, :, None]      # render_utils.py:131, two rounded ops
                 return net.forward(pts, rays[:, 8:11] if rays.shape[1] > 8 else None)
+
+        z_c = z
 
         raw = field(coarse_model, z)
         rgb, disp, acc, weights, _ = _Raw2OutputsFn.apply(raw, z, rays_d, noise0, bool(self.white_bkgd))

@@ -746,6 +746,11 @@ class CapturedTrainStep(_CapturedStep):
     Everything the step touches must stay alive and in place (models, optimizer state).  Needs nerf_shared_amd.optim.Adam
     (utils.get_optimizer) and models the training kernels cover.  Constructing it leaves parameters, moments and step
     counts as they were (the warm-up steps the capture needs are undone).
+    The step captures whatever the renderer does: with renderer.train_occupancy set (occupancy.TrainCull) it is captured
+    culled -- the fractions (the lists' capacities) are FROZEN at capture, the grid's bits are READ AT REPLAY, so
+    OccupancyGrid.refresh_from_density between replays is seen by the next one; the warm-up steps of the construction add
+    to the TrainCull's running totals.  Construct it with no autograd graph over the parameters alive (no render result of
+    an earlier eager step in a variable): such a graph pins the parameters' gradient accumulators to the stream it ran on.
 
         step = utils.CapturedTrainStep(renderer, H, W, K, chunk, coarse, fine, optimizer, N_rand)
         for i in range(n_iters):
@@ -805,6 +810,8 @@ class CapturedPoseStep(_CapturedStep):
     cam_transf.parameters() and frozen models (requires_grad_(False)): a field that asked for parameter gradients would
     take the training backward for gradients nobody steps.  Constructing it leaves the seven parameters, the moments and
     the step count as they were.
+    With renderer.train_occupancy set (occupancy.TrainCull) the step is captured culled, as CapturedTrainStep is: the
+    fractions are frozen at capture, the grid's bits are read at replay.
 
         cam = utils.CameraTransf().to(device)
         opt = optim.Adam(cam.parameters(), lr=lrate, betas=(0.9, 0.999))

@@ -4,7 +4,9 @@ white background, rendered analytically from poses on a camera circle, is learne
 coarse+fine NeRF pair with the reference's loop (main.py:67-112: random ray batches -> render ->
 mse(rgb) + mse(rgb0) -> Adam with exponential lr decay).  Prints PSNR on a held-out view.
 
-    python tools/train_demo.py [--steps 600] [--res 64] [--views 12]
+    python tools/train_demo.py [--steps 600] [--res 64] [--views 12] [--occupancy 32 --occupancy-warmup 200 --occupancy-refresh 16]
+
+--occupancy RES trains with an occupancy grid of RES^3 cells (occupancy.TrainCull, Renderer.train_occupancy; see train_culled).
 """
 import argparse
 import json
@@ -18,7 +20,9 @@ os.environ.setdefault("NERF_AMD_QUIET", "1")
 import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
-from nerf_shared_amd import render_utils, synth, utils  # noqa: E402
+from nerf_shared_amd import occupancy, render_utils, synth, utils  # noqa: E402
+
+SPHERE_BOX = [[-1.5, -1.5, -1.5], [1.5, 1.5, 1.5]]          # the unit sphere with room for the dilation
 
 
 def sphere_image(H, W, K, c2w, dev, radius=1.0, ss=1):
@@ -62,8 +66,109 @@ def write_blender_scene(root, H, W, poses, images, i_train, i_test):
             json.dump(meta, f)
 
 
+def train_culled(renderer, coarse, fine, opt, H, W, K, chunk, n_rand, next_batch, lr_at, first, steps, box, resolution,
+                 warmup=200, refresh=16, calibration_steps=8, slabs=8, margin=1.25, outside="empty", verbose=True):
+    """The training loop with an occupancy grid, steps [first, first + steps):
+      1. `warmup` steps through a captured DENSE step (utils.CapturedTrainStep): the field has to mean something first;
+      2. OccupancyGrid(box, resolution).fill_from_density([coarse, fine]);
+      3. `calibration_steps` eager steps at fraction 1.0 (no saving, but the live counts are exact), then TrainCull.calibrate();
+      4. a second captured step, now with Renderer.train_occupancy set: the fractions are frozen in it, the grid is not;
+      5. every `refresh` steps one of `slabs` slabs of the grid is re-marked from the models with a new seed
+         (refresh_from_density: in place, nothing synchronises), so the grid follows the models; the share of live cells and
+         the counts are then read (one synchronisation per refresh, and two soon after a capture) and, when the grid or the
+         live share has grown towards the frozen capacities, the fractions are set again and the step is captured again.
+    next_batch(i) -> (rays [2, n_rand, 3], target [n_rand, 3]); lr_at(i): the learning rate AFTER step i (main.py:108-112).
+    Returns (last loss, the TrainCull or None when the run ended inside the warm-up, its stats())."""
+    def set_lr(i):
+        for g in opt.param_groups:
+            g['lr'] = lr_at(i)
+
+    def eager_step(i):
+        # In a function of its own: NOTHING with autograd history may outlive it.  A render result left in a local of this
+        # loop would keep the parameters' AccumulateGrad nodes -- made on the stream this step ran on -- alive into the
+        # construction of the next captured step, whose backward would then hand its gradients to nodes of the default
+        # stream from inside a capture.
+        rays, target = next_batch(i)
+        opt.zero_grad(set_to_none=True)
+        rgb, _, _, extras = renderer.render_from_rays(H, W, K, chunk, rays, coarse, fine, retraw=True)
+        loss = utils.img2mse(rgb, target)
+        if 'rgb0' in extras:
+            loss = loss + utils.img2mse(extras['rgb0'], target)
+        loss.backward()
+        opt.sync_lr()                                        # (after a captured step the update reads the rate on the device)
+        opt.step()
+        return loss.detach()
+
+    loss, i, last = None, first, first + steps
+    renderer.train_occupancy = None
+    if min(warmup, steps) > 0:
+        dense = utils.CapturedTrainStep(renderer, H, W, K, chunk, coarse, fine, opt, n_rand)
+        while i < min(first + warmup, last):
+            loss = dense(*next_batch(i))
+            set_lr(i)
+            i += 1
+    if i >= last:
+        return loss, None, None
+    grid = occupancy.OccupancyGrid(box, resolution, outside=outside, device=next(coarse.parameters()).device)
+    grid.fill_from_density([coarse, fine])
+    cull = occupancy.TrainCull(grid)
+    renderer.train_occupancy = cull
+    for _ in range(min(calibration_steps, last - i)):
+        loss = eager_step(i)
+        set_lr(i)
+        i += 1
+    fractions = cull.calibrate(margin)
+    if verbose:
+        print("occupancy: %.1f %% of the cells live; capacities %.3f (coarse) %.3f (fine) of the samples"
+              % (100 * grid.occupied_fraction(), fractions[0], fractions[1]))
+
+    def capture():
+        before = cull.totals.clone()
+        step = utils.CapturedTrainStep(renderer, H, W, K, chunk, coarse, fine, opt, n_rand)
+        cull.totals.copy_(before)                            # (the construction's warm-up steps are not the run's)
+        return step
+
+    if i < last:
+        cull.stats(reset=True)
+        step, seen, captured_at, occupied = capture(), cull.stats(), i, grid.occupied_fraction()
+        while i < last:
+            loss = step(*next_batch(i))
+            set_lr(i)
+            i += 1
+            refreshed = refresh > 0 and (i - first) % refresh == 0
+            grown = 1.0
+            if refreshed:
+                grid.refresh_from_density([coarse, fine], cells=grid.slab((i - first) // refresh, slabs), seed=i)
+                grown = grid.occupied_fraction() / max(occupied, 1e-9)
+            if refreshed or i - captured_at in (4, 8):
+                # The capacities are frozen in the captured step; the field, and with it the refreshed grid, is not.  Two
+                # looks (each reads counts: a synchronisation per refresh, and two soon after a capture): the share of
+                # live cells BEFORE the next replay -- a refresh that grew the grid raises the capacities by as much at
+                # once --, and the live share of the steps since the last look.  Either one using up a quarter of the
+                # margin's headroom sets the fractions again and captures again.
+                now = cull.stats()
+                if now["coarse"]["total"] == seen["coarse"]["total"]:
+                    continue                                 # (no step since the last look: nothing to judge by)
+                share = {p: (now[p]["live"] - seen[p]["live"]) / max(now[p]["total"] - seen[p]["total"], 1) for p in cull.PASSES}
+                seen = now
+                tight = any(share[p] * grown * margin ** 0.75 > getattr(cull, p + "_fraction") for p in cull.PASSES
+                            if getattr(cull, p + "_fraction") < 1.0)
+                if tight or grown > margin ** 0.25:
+                    for p in cull.PASSES:
+                        setattr(cull, p + "_fraction", min(1.0, max(margin * share[p] * max(grown, 1.0), 1.0 / n_rand)))
+                    step, captured_at, occupied = capture(), i, grid.occupied_fraction()
+                    if verbose:
+                        print("step %d: capacities now %.3f (coarse) %.3f (fine)" % (i, cull.coarse_fraction, cull.fine_fraction))
+    stats = cull.stats()
+    for name, s in stats.items():
+        if s["overflow"] > 0.01 * max(s["live"], 1):
+            print("WARNING: %s pass: %d of %d live samples overflowed the list (treated as empty); raise the margin of calibrate()"
+                  % (name, s["overflow"], s["live"]), file=sys.stderr)
+    return loss, cull, stats
+
+
 def run(steps=600, res=64, views=12, n_rand=1024, seed=0, verbose=True, scene_dir=None, multires=10, multires_views=4,
-        lrate=5e-4, ss=1):
+        lrate=5e-4, ss=1, occupancy_res=None, occupancy_warmup=200, occupancy_refresh=16):
     """scene_dir: write the scene to disk in the Blender format first and train from what
     utils.load_datasets reads back (8-bit frames) instead of from the in-memory float images."""
     torch.manual_seed(seed)
@@ -102,7 +207,20 @@ def run(steps=600, res=64, views=12, n_rand=1024, seed=0, verbose=True, scene_di
     psnr0 = test_psnr()
     torch.cuda.synchronize()
     t0 = time.perf_counter()
-    for i in range(steps):
+    cull_stats = None
+    if occupancy_res:
+        bank = [rays_rgb, i_batch]
+
+        def next_batch(i):
+            batch_rays, target, bank[0], bank[1] = utils.sample_random_ray_batch(args, images, poses_t, bank[0], N_rand, use_batching,
+                                                                                 bank[1], i_train, (H, W, K[0][0]), K, 0, i)
+            return batch_rays, target
+
+        loss, _, cull_stats = train_culled(renderer, coarse, fine, opt, H, W, K, 32768, N_rand, next_batch,
+                                           lambda i: args.lrate * (0.1 ** (i / (args.lrate_decay * 1000))), 0, steps, SPHERE_BOX,
+                                           int(occupancy_res), occupancy_warmup, occupancy_refresh, verbose=verbose)
+        renderer.train_occupancy = None
+    for i in range(0 if occupancy_res else steps):          # the dense loop, eager (main.py:77-112)
         batch_rays, target, rays_rgb, i_batch = utils.sample_random_ray_batch(args, images, poses_t, rays_rgb, N_rand, use_batching,
                                                                               i_batch, i_train, (H, W, K[0][0]), K, 0, i)
         opt.zero_grad(set_to_none=True)
@@ -119,6 +237,8 @@ def run(steps=600, res=64, views=12, n_rand=1024, seed=0, verbose=True, scene_di
     dt = time.perf_counter() - t0
     out = {"steps": steps, "rays_per_step": n_rand, "train_s": dt, "steps_per_s": steps / dt,
            "psnr_before": psnr0, "psnr_after": test_psnr(), "final_loss": float(loss.detach())}
+    if occupancy_res:
+        out["occupancy"] = {"resolution": int(occupancy_res), "warmup": occupancy_warmup, "refresh": occupancy_refresh, "stats": cull_stats}
     return out, (coarse, fine, opt, args, renderer, (H, W, K), poses_t, images, i_test)
 
 
@@ -134,6 +254,11 @@ if __name__ == "__main__":
     ap.add_argument("--lrate", type=float, default=5e-4)
     ap.add_argument("--ss", type=int, default=1, help="ss x ss sub-pixel samples per ground-truth pixel")
     ap.add_argument("--quiet", action="store_true")
+    ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--occupancy", type=int, default=0, metavar="RES", help="train with an occupancy grid of RES^3 cells (0: dense)")
+    ap.add_argument("--occupancy-warmup", type=int, default=200, metavar="N", help="dense steps before the grid is filled")
+    ap.add_argument("--occupancy-refresh", type=int, default=16, metavar="K", help="re-mark a slab of the grid every K steps (0: never)")
     a = ap.parse_args()
-    print(json.dumps(run(a.steps, a.res, a.views, n_rand=a.n_rand, scene_dir=a.scene_dir, multires=a.multires,
-                         multires_views=a.multires_views, lrate=a.lrate, ss=a.ss, verbose=not a.quiet)[0]))
+    print(json.dumps(run(a.steps, a.res, a.views, n_rand=a.n_rand, seed=a.seed, scene_dir=a.scene_dir, multires=a.multires,
+                         multires_views=a.multires_views, lrate=a.lrate, ss=a.ss, verbose=not a.quiet, occupancy_res=a.occupancy or None,
+                         occupancy_warmup=a.occupancy_warmup, occupancy_refresh=a.occupancy_refresh)[0]))

@@ -47,6 +47,13 @@ def main():
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--ckpt", default=None, help="reference-format .tar to start from (with --iters 0: render only)")
     ap.add_argument("--render-path", type=int, default=0, help="also render this many poses of the scene's render path")
+    ap.add_argument("--occupancy", type=int, default=0, metavar="RES",
+                    help="train with an occupancy grid of RES^3 cells over --occupancy-box (tools/train_demo.py train_culled; 0: dense)")
+    ap.add_argument("--occupancy-warmup", type=int, default=200, metavar="N", help="dense steps before the grid is filled")
+    ap.add_argument("--occupancy-refresh", type=int, default=16, metavar="K", help="re-mark a slab of the grid every K steps (0: never)")
+    ap.add_argument("--occupancy-box", type=float, nargs=6, default=[-1.5, -1.5, -1.5, 1.5, 1.5, 1.5], metavar="V",
+                    help="lo_x lo_y lo_z hi_x hi_y hi_z in the coordinates the field is evaluated in (llff: NDC); outside it is empty "
+                         "for blender scenes and live for llff")
     a = ap.parse_args()
     dev = torch.device("cuda:0")
     torch.manual_seed(a.seed)
@@ -90,7 +97,22 @@ def main():
 
     torch.cuda.synchronize()
     t0 = time.perf_counter()
-    for i in range(start, start + a.iters):
+    cull_stats, culled = None, bool(a.occupancy and a.iters > 0)
+    if culled:
+        from tools import train_demo
+        bank = [rays_rgb, i_batch]
+
+        def next_batch(i):
+            batch_rays, target, bank[0], bank[1] = utils.sample_random_ray_batch(args, images_t, poses_t, bank[0], N_rand, use_batching,
+                                                                                 bank[1], i_train, hwf, K, 0, i)
+            return batch_rays, target
+
+        _, _, cull_stats = train_demo.train_culled(renderer, coarse, fine, optimizer, H, W, K, a.chunk, N_rand, next_batch,
+                                                   lambda i: a.lrate * (0.1 ** (i / (a.lrate_decay * 1000))), start, a.iters,
+                                                   [a.occupancy_box[:3], a.occupancy_box[3:]], a.occupancy, a.occupancy_warmup,
+                                                   a.occupancy_refresh, outside="live" if ndc else "empty")
+        renderer.train_occupancy = None
+    for i in range(start, start + (0 if culled else a.iters)):          # the dense loop, eager
         batch_rays, target, rays_rgb, i_batch = utils.sample_random_ray_batch(args, images_t, poses_t, rays_rgb, N_rand,
                                                                               use_batching, i_batch, i_train, hwf, K, 0, i)
         optimizer.zero_grad(set_to_none=True)
@@ -123,7 +145,8 @@ def main():
         n_path = len(renderer.render_from_batch_poses(H, W, K, a.chunk, list(rp), coarse, fine, False, os.path.join(a.out, "path"),
                                                       b_combine_as_video=True))
     print(json.dumps({"iters": a.iters, "train_s": train_s, "it_per_s": a.iters / max(train_s, 1e-9), "checkpoint": ckpt, "path_views": n_path,
-                      "test_views": len(frames), "test_psnr_mean": float(np.mean(psnr)), "test_psnr": psnr}))
+                      "test_views": len(frames), "test_psnr_mean": float(np.mean(psnr)), "test_psnr": psnr,
+                      **({"occupancy": cull_stats} if a.occupancy else {})}))
 
 
 if __name__ == "__main__":
