@@ -94,26 +94,9 @@ unsigned *tile_counter_for(bool deal, hipStream_t s) {
 }
 }  // namespace na
 
-struct nerf_amd_model {
+struct nerf_amd_model : DevTables {
     Program prog;
     int device = 0;
-    FragDesc *d_frags = nullptr;
-    TileDesc *d_tiles = nullptr;
-    LayerF32 *d_layers = nullptr;
-    TensorDesc *d_tensors = nullptr;
-    uint16_t *stream_bf16 = nullptr, *stream_s16 = nullptr, *stream_bwd = nullptr, *stream_split = nullptr;
-    FragDesc *d_frags_bwd = nullptr, *d_frags_split = nullptr, *d_frags_bwd_split = nullptr;
-    uint16_t *stream_bwd_split = nullptr;
-    float *bias_bf16 = nullptr, *stream_f32 = nullptr, *bias_f32 = nullptr, *bias_s16 = nullptr;
-    FragDesc *d_frags16 = nullptr;
-    TileDesc *d_tiles16 = nullptr;
-    TrainLayerF32 *d_tlayers = nullptr;  // train_f32.hip: per-layer descriptors and the transposed fp32 stream
-    float *stream_f32_t = nullptr;
-    // the folded s16 stream (program.h frags16_fold), its bias table and the fp32 FOLD tensor it is packed from
-    FragDesc *d_frags16_fold = nullptr;
-    TileDesc *d_tiles16_fold = nullptr;
-    uint16_t *stream_s16_fold = nullptr;
-    float *bias_s16_fold = nullptr, *fold_w = nullptr, *fold_b = nullptr;
     int fresh = 0;                       // NERF_AMD_COPY_* of the packed copies that hold the current parameters
 };
 
@@ -141,33 +124,27 @@ int nerf_amd_model_create(const nerf_amd_arch *arch, int device, nerf_amd_model 
     int rc;
     std::vector<TensorDesc> tensors_dev(p.tensors);      // + the FOLD tensor at p.fold_tensor (the pack kernels' table only)
     if (p.fold_tensor >= 0) tensors_dev.push_back({p.arch.W / 2, p.arch.W + p.input_ch_views});
-    if ((rc = upload(&m->d_frags, p.frags)) || (rc = upload(&m->d_tiles, p.tiles)) ||
-        (rc = upload(&m->d_frags16, p.frags16)) || (rc = upload(&m->d_tiles16, p.tiles16)) ||
-        (rc = upload(&m->d_frags_bwd, p.frags_bwd)) || (rc = upload(&m->d_frags_split, p.frags_split)) ||
-        (rc = upload(&m->d_frags_bwd_split, p.frags_bwd_split)) ||
-        (rc = upload(&m->d_frags16_fold, p.frags16_fold)) || (rc = upload(&m->d_tiles16_fold, p.tiles16_fold)) ||
-        (rc = upload(&m->d_layers, p.layers)) || (rc = upload(&m->d_tensors, tensors_dev)) || (rc = upload(&m->d_tlayers, p.tlayers))) {
+    rc = upload(&m->d_layers, p.layers);
+    if (!rc) rc = upload(&m->d_tensors, tensors_dev);
+    if (!rc) rc = upload(&m->d_tlayers, p.tlayers);
+    for (int i = 0; i < N_STREAMS && !rc; ++i)
+        if (!(rc = upload(&m->st[i].d_frags, p.streams[i].frags))) rc = upload(&m->st[i].d_tiles, p.streams[i].tiles);
+    if (rc) {
         nerf_amd_model_destroy(m);
         return rc;
     }
+    // (the streams of a model outside the fused family are empty: nothing is allocated for them)
     hipError_t e = hipSuccess;
-    if (p.bf16_ok) {
-        e = hipMalloc(reinterpret_cast<void **>(&m->stream_bf16), p.frags.size() * 1024);
-        if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&m->bias_bf16), p.tiles.size() * 32 * sizeof(float));
-        if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&m->stream_s16), p.frags16.size() * 1024);
-        if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&m->bias_s16), p.tiles16.size() * 16 * sizeof(float));
-        if (e == hipSuccess && !p.frags_bwd.empty())
-            e = hipMalloc(reinterpret_cast<void **>(&m->stream_bwd), p.frags_bwd.size() * 1024);
-        if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&m->stream_split), p.frags_split.size() * 1024);
-        if (e == hipSuccess && !p.frags16_fold.empty()) {
-            const size_t rows = (size_t)p.arch.W / 2, cols = (size_t)p.arch.W + p.input_ch_views;
-            e = hipMalloc(reinterpret_cast<void **>(&m->stream_s16_fold), p.frags16_fold.size() * 1024);
-            if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&m->bias_s16_fold), p.tiles16_fold.size() * 16 * sizeof(float));
-            if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&m->fold_w), rows * cols * sizeof(float));
-            if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&m->fold_b), rows * sizeof(float));
-        }
-        if (e == hipSuccess && !p.frags_bwd_split.empty())
-            e = hipMalloc(reinterpret_cast<void **>(&m->stream_bwd_split), p.frags_bwd_split.size() * 1024);
+    for (int i = 0; i < N_STREAMS && e == hipSuccess; ++i) {
+        const FragStream &fs = p.streams[i];
+        if (!fs.frags.empty()) e = hipMalloc(reinterpret_cast<void **>(&m->st[i].stream), fs.frags.size() * 1024);
+        if (e == hipSuccess && !fs.tiles.empty())
+            e = hipMalloc(reinterpret_cast<void **>(&m->st[i].bias), fs.tiles.size() * STREAMS[i].bias_rows * sizeof(float));
+    }
+    if (e == hipSuccess && m->st[ST_S16_FOLD].stream) {
+        const size_t rows = (size_t)p.arch.W / 2, cols = (size_t)p.arch.W + p.input_ch_views;
+        e = hipMalloc(reinterpret_cast<void **>(&m->fold_w), rows * cols * sizeof(float));
+        if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&m->fold_b), rows * sizeof(float));
     }
     if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&m->stream_f32), (size_t)p.f32_stream_floats * sizeof(float));
     if (e == hipSuccess && tile_counters_init(device) != NERF_AMD_OK) e = hipErrorOutOfMemory;      // the field kernel's ticket counters
@@ -197,15 +174,9 @@ int nerf_amd_model_update_copies(nerf_amd_model *m, const float *const *weights,
     std::memset(&wt, 0, sizeof(wt));
     std::memset(&bt, 0, sizeof(bt));
     for (int i = 0; i < n_tensors; ++i) { wt.p[i] = weights[i]; bt.p[i] = biases[i]; }
-    int rc = launch_pack(p, m->d_frags, m->d_tiles, m->d_layers, m->d_tensors, wt, bt,
-                         m->stream_bf16, m->bias_bf16, m->stream_f32, m->bias_f32,
-                         m->d_frags16, m->d_tiles16, m->stream_s16, m->bias_s16, m->d_frags_bwd, m->stream_bwd,
-                         m->d_frags_split, m->stream_split, m->d_frags_bwd_split, m->stream_bwd_split, m->d_tlayers, m->stream_f32_t,
-                         copies, s);
+    int rc = launch_pack(p, *m, wt, bt, copies, s);
     // the folded stream: launches of its own, only when asked for (a captured training step packs what it always packed)
-    if (!rc && (copies & NERF_AMD_COPY_BF16_FOLD) && m->stream_s16_fold)
-        rc = launch_pack_fold(p, m->d_frags16_fold, m->d_tiles16_fold, m->d_tensors, wt, bt, m->fold_w, m->fold_b, m->stream_s16_fold,
-                              m->bias_s16_fold, s);
+    if (!rc && (copies & NERF_AMD_COPY_BF16_FOLD) && m->st[ST_S16_FOLD].stream) rc = launch_pack_fold(p, *m, wt, bt, s);
     if (rc) return fail(rc, "pack launch failed");
     m->fresh = (others_current ? m->fresh : 0) | copies;
     return NERF_AMD_OK;
@@ -218,14 +189,10 @@ int nerf_amd_model_update(nerf_amd_model *m, const float *const *weights, const 
 
 void nerf_amd_model_destroy(nerf_amd_model *m) {
     if (!m) return;
-    (void)hipFree(m->d_frags); (void)hipFree(m->d_tiles); (void)hipFree(m->d_layers); (void)hipFree(m->d_tensors);
-    (void)hipFree(m->d_frags_bwd_split); (void)hipFree(m->stream_bwd_split);
-    (void)hipFree(m->d_frags_bwd); (void)hipFree(m->stream_bwd); (void)hipFree(m->d_frags_split); (void)hipFree(m->stream_split);
-    (void)hipFree(m->d_frags16); (void)hipFree(m->d_tiles16); (void)hipFree(m->stream_s16); (void)hipFree(m->bias_s16);
-    (void)hipFree(m->stream_bf16); (void)hipFree(m->bias_bf16); (void)hipFree(m->stream_f32); (void)hipFree(m->bias_f32);
-    (void)hipFree(m->d_tlayers); (void)hipFree(m->stream_f32_t);
-    (void)hipFree(m->d_frags16_fold); (void)hipFree(m->d_tiles16_fold); (void)hipFree(m->stream_s16_fold);
-    (void)hipFree(m->bias_s16_fold); (void)hipFree(m->fold_w); (void)hipFree(m->fold_b);
+    for (DevStream &d : m->st) { (void)hipFree(d.d_frags); (void)hipFree(d.d_tiles); (void)hipFree(d.stream); (void)hipFree(d.bias); }
+    (void)hipFree(m->d_layers); (void)hipFree(m->d_tensors); (void)hipFree(m->d_tlayers);
+    (void)hipFree(m->stream_f32); (void)hipFree(m->bias_f32); (void)hipFree(m->stream_f32_t);
+    (void)hipFree(m->fold_w); (void)hipFree(m->fold_b);
     delete m;
 }
 
@@ -243,19 +210,24 @@ int nerf_amd_model_out_ch(const nerf_amd_model *m) { return m ? m->prog.out_ch :
 
 int nerf_amd_pack_bf16_host(const nerf_amd_arch *arch, int shape, const float *const *weights, const float *const *biases,
                             int n_tensors, uint16_t *stream_out, int64_t *n_frags, float *bias_out, int64_t *n_bias) {
-    if (shape != 16 && shape != 32 && shape != 17 && shape != 18 && shape != 19 && shape != 20)
-        return fail(NERF_AMD_EINVAL, "shape must be 32 (32x32x16 stream), 16 (16x16x32 stream), 17 (backward stream), 18 (split-precision stream), 19 (split-precision backward stream) or 20 (folded 16x16x32 stream)");
+    const int id = stream_of_shape(shape);
+    if (id < 0) {
+        std::string msg;
+        for (const StreamInfo &info : STREAMS)
+            msg += (msg.empty() ? "shape must be " : ", ") + std::to_string(info.shape) + " (" + info.what + ")";
+        return fail(NERF_AMD_EINVAL, msg);
+    }
     if (!arch) return fail(NERF_AMD_EINVAL, "null argument");
     Program p;
     const char *err = "";
     if (build_program(*arch, p, &err) != 0) return fail(NERF_AMD_EINVAL, err);
     if (!p.bf16_ok) return fail(NERF_AMD_EUNSUPPORTED, "architecture has no fused bf16 program (needs D=8, W=256, skips=[4])");
-    if (shape == 20 && p.fold_tensor < 0) return fail(NERF_AMD_EUNSUPPORTED, "architecture has no view branch: nothing to fold");
-    if (n_frags) *n_frags = (int64_t)(shape == 20 ? p.frags16_fold.size() : shape == 19 ? p.frags_bwd_split.size() : shape == 18 ? p.frags_split.size() : shape == 17 ? p.frags_bwd.size() : shape == 16 ? p.frags16.size() : p.frags.size());
-    if (n_bias) *n_bias = (shape == 17 || shape == 18 || shape == 19) ? 0 : shape == 20 ? (int64_t)p.tiles16_fold.size() * 16 : shape == 16 ? (int64_t)p.tiles16.size() * 16 : (int64_t)p.tiles.size() * 32;
+    if (id == ST_S16_FOLD && p.fold_tensor < 0) return fail(NERF_AMD_EUNSUPPORTED, "architecture has no view branch: nothing to fold");
+    if (n_frags) *n_frags = (int64_t)p.streams[id].frags.size();
+    if (n_bias) *n_bias = (int64_t)p.streams[id].tiles.size() * STREAMS[id].bias_rows;
     if (stream_out || bias_out) {
         if (!weights || !biases || n_tensors != (int)p.tensors.size()) return fail(NERF_AMD_EINVAL, "bad parameter list");
-        pack_bf16_host(p, shape, weights, biases, stream_out, bias_out);
+        pack_bf16_host(p, (StreamId)id, weights, biases, stream_out, bias_out);
     }
     return NERF_AMD_OK;
 }
@@ -298,6 +270,15 @@ void set_model_constants(MlpArgs &a, const nerf_amd_model *m) {
     a.out_ch = p.out_ch;
 }
 
+// every packed copy of the parameters, where the kernels look for it
+void bind_streams(MlpArgs &a, const nerf_amd_model *m) {
+    a.stream_bf16 = m->st[ST_BF16_32].stream; a.bias_bf16 = m->st[ST_BF16_32].bias;
+    a.stream_s16 = m->st[ST_S16].stream; a.bias_s16 = m->st[ST_S16].bias;
+    a.stream_split = m->st[ST_SPLIT].stream;             // (its bias table is the s16 stream's)
+    a.stream_bwd = m->st[ST_BWD].stream; a.stream_bwd_split = m->st[ST_BWD_SPLIT].stream;
+    a.stream_f32 = m->stream_f32; a.bias_f32 = m->bias_f32;
+}
+
 // fold_mode: what tuning key 2 lets this caller do with the folded stream of a bf16 view-branch model of the fused family
 // (16x16x32 kernels).  FOLD_IF_CURRENT (the render path): taken when the folded copy holds the current parameters
 // (NERF_AMD_COPY_BF16_FOLD: asked for by whoever renders), else the unfolded stream as always.  FOLD_REQUIRED (key 2 = 2,
@@ -305,17 +286,15 @@ void set_model_constants(MlpArgs &a, const nerf_amd_model *m) {
 enum { FOLD_NEVER = 0, FOLD_IF_CURRENT = 1, FOLD_REQUIRED = 2 };
 int run_field(const nerf_amd_model *m, MlpArgs a, int precision, hipStream_t s, int fold_mode = FOLD_NEVER) {
     const Program &p = m->prog;
+    const FragStream &s32 = p.streams[ST_BF16_32], &s16 = p.streams[ST_S16], &sfold = p.streams[ST_S16_FOLD];
     if (int rc0 = need_copy(m, copy_for(precision))) return rc0;
     const int variant = g_variant.load(std::memory_order_relaxed);
-    const bool foldable = precision == NERF_AMD_PREC_BF16 && m->stream_s16_fold && nerf_amd_model_supports_bf16(m) &&
+    const bool foldable = precision == NERF_AMD_PREC_BF16 && m->st[ST_S16_FOLD].stream && nerf_amd_model_supports_bf16(m) &&
                           variant < 100 && variant != 40;      // (40: the round-1 shape of the A/B table has no folded twin)
     if (fold_mode == FOLD_REQUIRED && foldable)
         if (int rc0 = need_copy(m, NERF_AMD_COPY_BF16_FOLD)) return rc0;
     const bool fold = fold_mode != FOLD_NEVER && foldable && (m->fresh & NERF_AMD_COPY_BF16_FOLD);
-    a.stream_bf16 = m->stream_bf16; a.bias_bf16 = m->bias_bf16;
-    a.stream_s16 = m->stream_s16; a.bias_s16 = m->bias_s16;
-    a.stream_split = m->stream_split;
-    a.stream_f32 = m->stream_f32; a.bias_f32 = m->bias_f32;
+    bind_streams(a, m);
     set_model_constants(a, m);
     if (p.arch.use_viewdirs && !a.viewdirs) return fail(NERF_AMD_EINVAL, "model has a view branch but no viewdirs were given");
     if (!p.arch.use_viewdirs) a.viewdirs = nullptr;
@@ -348,22 +327,22 @@ int run_field(const nerf_amd_model *m, MlpArgs a, int precision, hipStream_t s, 
         if (!nerf_amd_model_supports_bf16(m))
             return fail(NERF_AMD_EUNSUPPORTED, "fused bf16 kernel needs D=8, W=256, skips=[4], multires/views in {(10,4),(15,6)}; use NERF_AMD_PREC_FP32");
         if (g_variant >= 100)   // A/B: the first-generation 32x32x16 kernel
-            rc = launch_mlp_bf16(a, p.arch.multires, p.arch.multires_views, p.arch.use_viewdirs, p.n_frags_used, (int)p.tiles.size(), s);
+            rc = launch_mlp_bf16(a, p.arch.multires, p.arch.multires_views, p.arch.use_viewdirs, s32.n_used, (int)s32.tiles.size(), s);
         else {
             if (fold) {
-                a.stream_s16 = m->stream_s16_fold; a.bias_s16 = m->bias_s16_fold;
-                rc = launch_mlp_bf16_s16(a, p.arch.multires, p.arch.multires_views, 1, p.n_frags16_fold_used, (int)p.tiles16_fold.size(), s, true);
+                a.stream_s16 = m->st[ST_S16_FOLD].stream; a.bias_s16 = m->st[ST_S16_FOLD].bias;
+                rc = launch_mlp_bf16_s16(a, p.arch.multires, p.arch.multires_views, 1, sfold.n_used, (int)sfold.tiles.size(), s, true);
             } else
-            rc = launch_mlp_bf16_s16(a, p.arch.multires, p.arch.multires_views, p.arch.use_viewdirs, p.n_frags16_used, (int)p.tiles16.size(), s);
+            rc = launch_mlp_bf16_s16(a, p.arch.multires, p.arch.multires_views, p.arch.use_viewdirs, s16.n_used, (int)s16.tiles.size(), s);
             if (rc == NERF_AMD_EUNSUPPORTED)   // e.g. output_ch > 16: the 32x32x16 kernel covers it
-                rc = launch_mlp_bf16(a, p.arch.multires, p.arch.multires_views, p.arch.use_viewdirs, p.n_frags_used, (int)p.tiles.size(), s);
+                rc = launch_mlp_bf16(a, p.arch.multires, p.arch.multires_views, p.arch.use_viewdirs, s32.n_used, (int)s32.tiles.size(), s);
         }
     } else if (precision == NERF_AMD_PREC_FP32) {
         rc = launch_mlp_f32(a, s);
     } else if (precision == NERF_AMD_PREC_FP32_SPLIT) {
         if (!nerf_amd_model_supports_split(m))
             return fail(NERF_AMD_EUNSUPPORTED, "split-precision kernel needs D=8, W=256, skips=[4], multires/views in {(10,4),(15,6)} (or 10 / 15 without a view branch, output_ch <= 16); use NERF_AMD_PREC_FP32");
-        rc = launch_mlp_split(a, p.arch.multires, p.arch.multires_views, p.arch.use_viewdirs, p.n_frags_split_used, (int)p.tiles16.size(), s);
+        rc = launch_mlp_split(a, p.arch.multires, p.arch.multires_views, p.arch.use_viewdirs, p.streams[ST_SPLIT].n_used, (int)s16.tiles.size(), s);
     } else {
         return fail(NERF_AMD_EINVAL, "unknown precision");
     }
@@ -464,7 +443,7 @@ int nerf_amd_field_forward_train(const nerf_amd_model *m, const float *pts, cons
         if ((!pts && (!rays || !z_vals)) || !raw || !workspace || workspace_bytes < train_f32_workspace_bytes(m->prog, P))
             return fail(NERF_AMD_EINVAL, "null pointer or workspace too small");
         MlpArgs a{};
-        a.stream_f32 = m->stream_f32; a.bias_f32 = m->bias_f32;
+        bind_streams(a, m);
         set_model_constants(a, m);
         set_inputs(a, pts, viewdirs, rays, ray_ch, z_vals, vd);
         a.P = P; a.S = S; a.out = raw;
@@ -479,13 +458,15 @@ int nerf_amd_field_forward_train(const nerf_amd_model *m, const float *pts, cons
     if ((!pts && (!rays || !z_vals)) || !raw || !workspace || workspace_bytes < train_workspace_bytes(m->prog, P, split))
         return fail(NERF_AMD_EINVAL, "null pointer or workspace too small");
     MlpArgs a{};
-    a.stream_s16 = m->stream_s16; a.bias_s16 = m->bias_s16; a.stream_split = m->stream_split;
+    bind_streams(a, m);
     set_inputs(a, pts, viewdirs, rays, ray_ch, z_vals, vd);
     a.P = P; a.S = S; a.out = raw; a.out_ch = m->prog.out_ch;
     train_fill_args(m->prog, P, workspace, &a, split);
     const nerf_amd_arch &ar = m->prog.arch;
-    int rc = split ? launch_mlp_split_save(a, ar.multires, ar.multires_views, vd, m->prog.n_frags_split_used, (int)m->prog.tiles16.size(), static_cast<hipStream_t>(stream))
-                   : launch_mlp_bf16_s16_save(a, ar.multires, ar.multires_views, vd, m->prog.n_frags16_used, (int)m->prog.tiles16.size(), static_cast<hipStream_t>(stream));
+    const FragStream &fs = m->prog.streams[split ? ST_SPLIT : ST_S16];
+    const int n_tiles = (int)m->prog.streams[ST_S16].tiles.size();
+    int rc = split ? launch_mlp_split_save(a, ar.multires, ar.multires_views, vd, fs.n_used, n_tiles, static_cast<hipStream_t>(stream))
+                   : launch_mlp_bf16_s16_save(a, ar.multires, ar.multires_views, vd, fs.n_used, n_tiles, static_cast<hipStream_t>(stream));
     return rc ? fail(rc, "training forward launch failed") : NERF_AMD_OK;
 }
 
@@ -528,13 +509,14 @@ static int field_backward(const nerf_amd_model *m, const float *g_raw, const flo
         return fail(NERF_AMD_EINVAL, "null pointer or workspace too small");
     hipStream_t s = static_cast<hipStream_t>(stream);
     MlpArgs a{};
-    a.stream_bwd = m->stream_bwd; a.stream_bwd_split = m->stream_bwd_split; a.g_raw = g_raw; a.P = n_points; a.S = S; a.out_ch = m->prog.out_ch;
+    bind_streams(a, m);
+    a.g_raw = g_raw; a.P = n_points; a.S = S; a.out_ch = m->prog.out_ch;
     set_inputs(a, pts, viewdirs, rays, ray_ch, z_vals, vd);
     a.g_pts = g_pts; a.g_rays = g_rays; a.g_vd = vd ? g_viewdirs : nullptr;
     train_fill_args(m->prog, n_points, workspace, &a, split);
     const nerf_amd_arch &ar = m->prog.arch;
-    int rc = split ? launch_mlp_bwd_split(a, ar.multires, ar.multires_views, vd, m->prog.n_frags_bwd_split_used, s)
-                   : launch_mlp_bwd_s16(a, ar.multires, ar.multires_views, vd, m->prog.n_frags_bwd_used, s);
+    int rc = split ? launch_mlp_bwd_split(a, ar.multires, ar.multires_views, vd, m->prog.streams[ST_BWD_SPLIT].n_used, s)
+                   : launch_mlp_bwd_s16(a, ar.multires, ar.multires_views, vd, m->prog.streams[ST_BWD].n_used, s);
     if (rc) return fail(rc, "backward kernel launch failed");
     if (!with_params) return NERF_AMD_OK;
     rc = train_param_grads(m->prog, n_points, workspace, grad_weights, grad_biases, m->device, s, split, g_raw);
@@ -576,7 +558,7 @@ const char *NO_VIEW_BRANCH = "density entry points take a model WITHOUT view bra
 
 bool density_fused_covers(const nerf_amd_model *m, int precision) {
     const nerf_amd_arch &a = m->prog.arch;
-    return precision == NERF_AMD_PREC_BF16 && fused_program(m->prog) && !m->prog.frags_bwd.empty() &&
+    return precision == NERF_AMD_PREC_BF16 && fused_program(m->prog) && !m->prog.streams[ST_BWD].frags.empty() &&
            density_grad_fused_supported(a.multires, a.use_viewdirs, m->prog.out_ch);
 }
 bool density_takes_fused(const nerf_amd_model *m, int precision) {
@@ -647,9 +629,9 @@ int nerf_amd_density_value_grad(const nerf_amd_model *m, const float *pts, int64
         if (n == 0) return NERF_AMD_OK;
         if (!pts || !sigma || !grad) return fail(NERF_AMD_EINVAL, "null pts/sigma/grad");
         MlpArgs a{};
-        a.stream_s16 = m->stream_s16; a.bias_s16 = m->bias_s16; a.stream_bwd = m->stream_bwd;
+        bind_streams(a, m);
         a.pts = pts; a.P = n; a.S = 1; a.out = sigma; a.out_ch = och; a.g_pts = grad;
-        int rc = launch_density_grad(a, m->prog.arch.multires, m->prog.n_frags16_used, (int)m->prog.tiles16.size(), m->prog.n_frags_bwd_used, s);
+        int rc = launch_density_grad(a, m->prog.arch.multires, m->prog.streams[ST_S16].n_used, (int)m->prog.streams[ST_S16].tiles.size(), m->prog.streams[ST_BWD].n_used, s);
         return rc ? fail(rc, "fused density kernel launch failed") : NERF_AMD_OK;
     }
     // two launches: the training forward (saves the activations), then the dX chain alone with dL/draw = 1 in the sigma column

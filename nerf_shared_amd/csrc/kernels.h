@@ -94,19 +94,30 @@ int launch_embed(const float *x, int64_t n, int multires, float *out, hipStream_
 constexpr int MAX_TENSORS = 72;     // D <= 64 pts_linears + 4 heads
 struct PtrTable { const float *p[MAX_TENSORS]; };
 
-// pack.hip
-int launch_pack(const Program &p, const FragDesc *d_frags, const TileDesc *d_tiles, const LayerF32 *d_layers,
-                const TensorDesc *d_tensors, const PtrTable &d_weight_ptrs, const PtrTable &d_bias_ptrs,
-                uint16_t *stream_bf16, float *bias_bf16, float *stream_f32, float *bias_f32,
-                const FragDesc *d_frags16, const TileDesc *d_tiles16, uint16_t *stream_s16, float *bias_s16,
-                const FragDesc *d_frags_bwd, uint16_t *stream_bwd, const FragDesc *d_frags_split, uint16_t *stream_split,
-                const FragDesc *d_frags_bwd_split, uint16_t *stream_bwd_split, const TrainLayerF32 *d_tlayers, float *stream_f32_t, int copies, hipStream_t s);
-// the folded s16 stream (program.h frags16_fold): fold_kernel into the model's scratch tensor, then its fragments and bias
-// tiles; d_tensors has the FOLD tensor's entry at p.fold_tensor.  A no-op for a model with nothing to fold.
-int launch_pack_fold(const Program &p, const FragDesc *d_frags16_fold, const TileDesc *d_tiles16_fold, const TensorDesc *d_tensors,
-                     PtrTable d_weight_ptrs, PtrTable d_bias_ptrs, float *fold_w, float *fold_b, uint16_t *stream_s16_fold,
-                     float *bias_s16_fold, hipStream_t s);
-void pack_bf16_host(const Program &p, int shape, const float *const *w, const float *const *b, uint16_t *stream, float *bias);
+// The device side of a model's packed copies (the base of nerf_amd_model, capi.hip): per stream of program.h the
+// descriptor tables and the buffers the pack kernel fills from them, then the fp32 program's.
+struct DevStream {
+    FragDesc *d_frags = nullptr;
+    TileDesc *d_tiles = nullptr;
+    uint16_t *stream = nullptr;      // frags.size() KiB; null for an empty stream
+    float *bias = nullptr;           // [tiles.size()][STREAMS[].bias_rows]; null without a bias table
+};
+struct DevTables {
+    DevStream st[N_STREAMS];
+    LayerF32 *d_layers = nullptr;
+    TensorDesc *d_tensors = nullptr;     // + the FOLD tensor's entry at Program::fold_tensor
+    TrainLayerF32 *d_tlayers = nullptr;  // train_f32.hip: per-layer descriptors and the transposed fp32 stream
+    float *stream_f32 = nullptr, *bias_f32 = nullptr, *stream_f32_t = nullptr;
+    float *fold_w = nullptr, *fold_b = nullptr;      // the fp32 FOLD tensor that ST_S16_FOLD is packed from
+};
+
+// pack.hip.  copies: NERF_AMD_COPY_* without the fold; a copy that is not asked for costs nothing.
+int launch_pack(const Program &p, const DevTables &t, const PtrTable &d_weight_ptrs, const PtrTable &d_bias_ptrs, int copies,
+                hipStream_t s);
+// the folded s16 stream (program.h ST_S16_FOLD): fold_kernel into the model's scratch tensor, then its fragments and bias
+// tiles.  A no-op for a model with nothing to fold.
+int launch_pack_fold(const Program &p, const DevTables &t, PtrTable d_weight_ptrs, PtrTable d_bias_ptrs, hipStream_t s);
+void pack_bf16_host(const Program &p, StreamId id, const float *const *w, const float *const *b, uint16_t *stream, float *bias);
 int launch_mlp_bf16_s16(const MlpArgs &a, int multires, int multires_views, int use_viewdirs,
                         int n_frags_used, int n_tiles, hipStream_t s, bool fold = false);
 // training kernels: the view-branch model with multires 10/4 or 15/6, the output_linear model with multires 10 or 15

@@ -93,66 +93,65 @@ NA_HD inline int frag_source(const FragDesc &d, int lane, int j, int n_out, int 
     return d.col_base + c;
 }
 
-// Every packed copy of a model from ONE launch (a re-pack follows every optimizer step of a training loop, where six
-// small launches cost more on the host than on the GPU): block ranges select the job.
-struct PackJobs {
-    const FragDesc *frags_bwd, *frags16, *frags, *frags_split, *frags_bwd_split;
-    const TileDesc *tiles16, *tiles;
-    const LayerF32 *layers;
-    const TrainLayerF32 *tlayers;
-    const TensorDesc *tensors;
-    uint16_t *stream_bwd, *stream_s16, *stream_bf16, *stream_split, *stream_bwd_split;
-    float *bias_s16, *bias_bf16, *stream_f32, *bias_f32, *stream_f32_t;
-    int n_bwd, n16, n32, n_split, n_bwd_split, n_tiles16, n_tiles, n_layers, n_layers_t;
-    int b_bias16, b_bias32;          // blocks of the two bias tables
-};
-constexpr int PACK_F32_BLOCKS = 32;  // per layer
-
-__device__ __forceinline__ void pack_frag(const FragDesc *frags, int n, const TensorDesc *tensors, const float *const *weights,
-                                          uint16_t *stream) {
-    const FragDesc d = frags[n];
-    const int lane = threadIdx.x >> 3, j = threadIdx.x & 7;
+// Element (lane, j) of fragment d, packed from the tensor it names.
+NA_HD inline uint16_t frag_value(const FragDesc d, int lane, int j, const TensorDesc *tensors, const float *const *weights) {
     int row;
     const TensorDesc t = tensors[d.tensor];
     const int col = frag_source(d, lane, j, t.n_out, &row);
-    const float v = col < 0 ? 0.0f : weights[d.tensor][(int64_t)row * t.n_in + col];
-    stream[(int64_t)n * 512 + threadIdx.x] = pack_value(v, d.part);
+    return pack_value(col < 0 ? 0.0f : weights[d.tensor][(int64_t)row * t.n_in + col], d.part);
 }
+// Element e of a bias table of `rows`-row tiles (program.h STREAMS: 16 natural rows, or the 32 of a 32x32x16 tile as [h][r]).
+NA_HD inline float bias_value(const TileDesc *tiles, int rows, int e, const TensorDesc *tensors, const float *const *biases) {
+    const TileDesc t = tiles[e >> (rows == 32 ? 5 : 4)];
+    const int row = t.row0 + bias_tile_row(e & (rows - 1), rows);
+    return row < tensors[t.tensor].n_out ? biases[t.tensor][row] : 0.0f;
+}
+
+// Every packed copy of a model from ONE launch (a re-pack follows every optimizer step of a training loop, where six
+// small launches cost more on the host than on the GPU).  Per stream of program.h a fragment job (one block per fragment)
+// and a bias job (512 elements per block); the launcher lays their block ranges out one after the other and hands the
+// kernel the end of each (a job that is not asked for ends where it starts), side by side in front of the arguments: a
+// block finds its job with one load.
+struct FragJob { const FragDesc *frags; uint16_t *out; };
+struct BiasJob { const TileDesc *tiles; float *out; int n, rows; };              // n elements in tiles of `rows` rows
+struct PackJobs {
+    int end[2 * N_STREAMS];          // first block behind fragment job i, then behind bias job i
+    const TensorDesc *tensors;
+    FragJob frag[N_STREAMS];
+    BiasJob bias[N_STREAMS];
+    const LayerF32 *layers;          // the fp32 streams: from block end[2 * N_STREAMS - 1] on
+    const TrainLayerF32 *tlayers;
+    float *stream_f32, *bias_f32, *stream_f32_t;
+    int n_layers, n_layers_t;
+};
+constexpr int PACK_F32_BLOCKS = 32;  // per layer
+static_assert(sizeof(PackJobs) + 2 * sizeof(PtrTable) <= 4096, "kernel-argument block of pack_all_kernel");
 
 __global__ __launch_bounds__(512) void pack_all_kernel(PackJobs J, PtrTable weights_tab, PtrTable biases_tab) {
     const float *const *weights = weights_tab.p;
     const float *const *biases = biases_tab.p;
     int b = blockIdx.x;
-    if (b < J.n_bwd) { pack_frag(J.frags_bwd, b, J.tensors, weights, J.stream_bwd); return; }
-    b -= J.n_bwd;
-    if (b < J.n16) { pack_frag(J.frags16, b, J.tensors, weights, J.stream_s16); return; }
-    b -= J.n16;
-    if (b < J.n32) { pack_frag(J.frags, b, J.tensors, weights, J.stream_bf16); return; }
-    b -= J.n32;
-    if (b < J.n_split) { pack_frag(J.frags_split, b, J.tensors, weights, J.stream_split); return; }
-    b -= J.n_split;
-    if (b < J.n_bwd_split) { pack_frag(J.frags_bwd_split, b, J.tensors, weights, J.stream_bwd_split); return; }
-    b -= J.n_bwd_split;
-    if (b < J.b_bias16) {            // [tile][16 rows], natural row order
-        const int e = b * 512 + threadIdx.x;
-        if (e < J.n_tiles16 * 16) {
-            const TileDesc t = J.tiles16[e >> 4];
-            const int row = t.row0 + (e & 15);
-            J.bias_s16[e] = row < J.tensors[t.tensor].n_out ? biases[t.tensor][row] : 0.0f;
-        }
+    // Unrolled: every job is read from the kernel arguments at a compile-time offset, so J is never copied to scratch.  One
+    // test finds the kind of job, then one copy of the packing code runs on the job picked among its kind.
+    if (b < J.end[N_STREAMS - 1]) {
+        FragJob fj = J.frag[0];
+#pragma unroll
+        for (int i = 1; i < N_STREAMS; ++i)
+            if ((int)blockIdx.x >= J.end[i - 1]) { fj = J.frag[i]; b = blockIdx.x - J.end[i - 1]; }
+        fj.out[(int64_t)b * 512 + threadIdx.x] = frag_value(fj.frags[b], threadIdx.x >> 3, threadIdx.x & 7, J.tensors, weights);
         return;
     }
-    b -= J.b_bias16;
-    if (b < J.b_bias32) {            // [tile][h][r] of the 32x32x16 kernel
+    if (b < J.end[2 * N_STREAMS - 1]) {
+        BiasJob bj = J.bias[0];
+        b -= J.end[N_STREAMS - 1];
+#pragma unroll
+        for (int i = 1; i < N_STREAMS; ++i)
+            if ((int)blockIdx.x >= J.end[N_STREAMS + i - 1]) { bj = J.bias[i]; b = blockIdx.x - J.end[N_STREAMS + i - 1]; }
         const int e = b * 512 + threadIdx.x;
-        if (e < J.n_tiles * 32) {
-            const TileDesc t = J.tiles[e >> 5];
-            const int row = t.row0 + acc_row(e & 15, (e >> 4) & 1);
-            J.bias_bf16[e] = row < J.tensors[t.tensor].n_out ? biases[t.tensor][row] : 0.0f;
-        }
+        if (e < bj.n) bj.out[e] = bias_value(bj.tiles, bj.rows, e, J.tensors, biases);
         return;
     }
-    b -= J.b_bias32;
+    b -= J.end[2 * N_STREAMS - 1];
     // fp32 stream: blocks of 256 values = one (tile, group) of a layer; a 512-thread block packs two at a time
     if (b >= J.n_layers * PACK_F32_BLOCKS) {
         // the transposed fp32 stream of train_f32.hip: tiles over the layer's INPUT features, k over its outputs
@@ -187,7 +186,7 @@ __global__ __launch_bounds__(512) void pack_all_kernel(PackJobs J, PtrTable weig
         J.bias_f32[L.bias_off + i] = i < L.n_out ? biases[L.tensor][i] : 0.0f;
 }
 
-// The fold of feature_linear into views_linears.0 (program.h, frags16_fold): row o of the FOLD tensor,
+// The fold of feature_linear into views_linears.0 (program.h, ST_S16_FOLD): row o of the FOLD tensor,
 //   fold_w[o][i] = sum_k Wv[o][k] Wf[k][i] (i < W),  fold_w[o][W + j] = Wv[o][W + j],  fold_b[o] = sum_k Wv[o][k] bf[k] + bv[o],
 // from the fp32 parameters, k ascending in one fp32 fma chain: deterministic, and exact on small-integer weights.
 // 8.4 M MAC once per weight change; one block per row.  fold_row is shared with the host twin.
@@ -206,167 +205,84 @@ __global__ __launch_bounds__(256) void fold_kernel(const float *wf, const float 
     if (threadIdx.x == 0) fold_b[o] = fold_dot(row, bf, 1, W) + bv[o];
 }
 
-// The folded stream and its bias table: the tables' entry p.fold_tensor is the FOLD tensor.
-__global__ __launch_bounds__(512) void pack_fold_kernel(const FragDesc *frags, int n_frags, const TileDesc *tiles, int n_tiles,
-                                                        const TensorDesc *tensors, PtrTable weights_tab, PtrTable biases_tab,
-                                                        uint16_t *stream, float *bias) {
-    const int b = blockIdx.x;
-    if (b < n_frags) { pack_frag(frags, b, tensors, weights_tab.p, stream); return; }
-    const int e = (b - n_frags) * 512 + threadIdx.x;
-    if (e < n_tiles * 16) {
-        const TileDesc t = tiles[e >> 4];
-        const int row = t.row0 + (e & 15);
-        bias[e] = row < tensors[t.tensor].n_out ? biases_tab.p[t.tensor][row] : 0.0f;
+namespace {
+// The jobs of the streams whose copy bit (or, for the bias table, its other reader's) is in `copies`, and their blocks.
+PackJobs stream_jobs(const Program &p, const DevTables &t, int copies) {
+    PackJobs J{};
+    J.tensors = t.d_tensors;
+    int blocks = 0;
+    for (int i = 0; i < N_STREAMS; ++i) {
+        J.frag[i] = {t.st[i].d_frags, t.st[i].stream};
+        J.end[i] = blocks += copies & STREAMS[i].copy ? (int)p.streams[i].frags.size() : 0;
     }
+    for (int i = 0; i < N_STREAMS; ++i) {
+        const bool wanted = copies & (STREAMS[i].copy | STREAMS[i].bias_copy);
+        J.bias[i] = {t.st[i].d_tiles, t.st[i].bias, wanted ? (int)p.streams[i].tiles.size() * STREAMS[i].bias_rows : 0, STREAMS[i].bias_rows};
+        J.end[N_STREAMS + i] = blocks += (J.bias[i].n + 511) / 512;
+    }
+    return J;
 }
 
-int launch_pack_fold(const Program &p, const FragDesc *d_frags16_fold, const TileDesc *d_tiles16_fold, const TensorDesc *d_tensors,
-                     PtrTable d_w, PtrTable d_b, float *fold_w, float *fold_b, uint16_t *stream_s16_fold, float *bias_s16_fold,
-                     hipStream_t s) {
-    if (p.fold_tensor < 0 || p.frags16_fold.empty()) return NERF_AMD_OK;          // nothing to fold
-    if (p.fold_tensor >= MAX_TENSORS) return NERF_AMD_EINVAL;
-    const int D = p.arch.D, W = p.arch.W;
-    hipLaunchKernelGGL(fold_kernel, dim3(W / 2), dim3(256), 0, s, d_w.p[D], d_b.p[D], d_w.p[D + 2], d_b.p[D + 2], W,
-                       p.input_ch_views, fold_w, fold_b);
-    d_w.p[p.fold_tensor] = fold_w;
-    d_b.p[p.fold_tensor] = fold_b;
-    const int n_frags = (int)p.frags16_fold.size(), n_tiles = (int)p.tiles16_fold.size();
-    hipLaunchKernelGGL(pack_fold_kernel, dim3(n_frags + (n_tiles * 16 + 511) / 512), dim3(512), 0, s, d_frags16_fold, n_frags,
-                       d_tiles16_fold, n_tiles, d_tensors, d_w, d_b, stream_s16_fold, bias_s16_fold);
-    return hipGetLastError() == hipSuccess ? NERF_AMD_OK : NERF_AMD_EHIP;
-}
-
-int launch_pack(const Program &p, const FragDesc *d_frags, const TileDesc *d_tiles, const LayerF32 *d_layers,
-                const TensorDesc *d_tensors, const PtrTable &d_w, const PtrTable &d_b,
-                uint16_t *stream_bf16, float *bias_bf16, float *stream_f32, float *bias_f32,
-                const FragDesc *d_frags16, const TileDesc *d_tiles16, uint16_t *stream_s16, float *bias_s16,
-                const FragDesc *d_frags_bwd, uint16_t *stream_bwd, const FragDesc *d_frags_split, uint16_t *stream_split,
-                const FragDesc *d_frags_bwd_split, uint16_t *stream_bwd_split, const TrainLayerF32 *d_tlayers, float *stream_f32_t,
-                int copies, hipStream_t s) {
-    PackJobs J;
-    J.frags_bwd_split = d_frags_bwd_split; J.stream_bwd_split = stream_bwd_split;
-    J.frags_bwd = d_frags_bwd; J.frags16 = d_frags16; J.frags = d_frags; J.frags_split = d_frags_split;
-    J.stream_split = stream_split;
-    J.tiles16 = d_tiles16; J.tiles = d_tiles; J.layers = d_layers; J.tensors = d_tensors;
-    J.stream_bwd = stream_bwd; J.stream_s16 = stream_s16; J.stream_bf16 = stream_bf16;
-    J.bias_s16 = bias_s16; J.bias_bf16 = bias_bf16; J.stream_f32 = stream_f32; J.bias_f32 = bias_f32;
-    // copies: NERF_AMD_COPY_* (include/nerf_amd.h); a job that is not asked for gets no blocks
-    const bool c_bf16 = copies & NERF_AMD_COPY_BF16, c_split = copies & NERF_AMD_COPY_SPLIT;
-    J.n_bwd = p.bf16_ok && (copies & NERF_AMD_COPY_BWD) ? (int)p.frags_bwd.size() : 0;
-    J.n16 = p.bf16_ok && c_bf16 ? (int)p.frags16.size() : 0;
-    J.n32 = p.bf16_ok && c_bf16 ? (int)p.frags.size() : 0;
-    J.n_split = p.bf16_ok && c_split ? (int)p.frags_split.size() : 0;
-    J.n_bwd_split = p.bf16_ok && (copies & NERF_AMD_COPY_BWD_SPLIT) ? (int)p.frags_bwd_split.size() : 0;
-    J.n_tiles16 = p.bf16_ok && (c_bf16 || c_split) ? (int)p.tiles16.size() : 0;       // the 16-row bias table serves both
-    J.n_tiles = p.bf16_ok && c_bf16 ? (int)p.tiles.size() : 0;
-    J.n_layers = (copies & NERF_AMD_COPY_FP32) ? (int)p.layers.size() : 0;
-    J.n_layers_t = (copies & NERF_AMD_COPY_FP32_BWD) && stream_f32_t ? (int)p.layers.size() : 0;
-    J.tlayers = d_tlayers; J.stream_f32_t = stream_f32_t;
-    J.b_bias16 = (J.n_tiles16 * 16 + 511) / 512;
-    J.b_bias32 = (J.n_tiles * 32 + 511) / 512;
-    const unsigned grid = (unsigned)(J.n_bwd + J.n16 + J.n32 + J.n_split + J.n_bwd_split + J.b_bias16 + J.b_bias32 + (J.n_layers + J.n_layers_t) * PACK_F32_BLOCKS);
+int launch_jobs(const PackJobs &J, const PtrTable &d_w, const PtrTable &d_b, hipStream_t s) {
+    const unsigned grid = (unsigned)(J.end[2 * N_STREAMS - 1] + (J.n_layers + J.n_layers_t) * PACK_F32_BLOCKS);
     if (grid == 0) return NERF_AMD_OK;
     hipLaunchKernelGGL(pack_all_kernel, dim3(grid), dim3(512), 0, s, J, d_w, d_b);
     return hipGetLastError() == hipSuccess ? NERF_AMD_OK : NERF_AMD_EHIP;
 }
+}  // namespace
 
-void pack_bf16_host(const Program &p, int shape, const float *const *w, const float *const *b,
-                    uint16_t *stream, float *bias) {
-    if (shape == 20) {       // folded s16 stream and its bias table: the FOLD tensor first, like fold_kernel
+// The folded stream and its bias table, by launches of their own (a captured training step packs exactly what it always
+// packed): the tables' entry p.fold_tensor is the FOLD tensor.
+int launch_pack_fold(const Program &p, const DevTables &t, PtrTable d_w, PtrTable d_b, hipStream_t s) {
+    if (p.fold_tensor < 0 || p.streams[ST_S16_FOLD].frags.empty()) return NERF_AMD_OK;          // nothing to fold
+    if (p.fold_tensor >= MAX_TENSORS) return NERF_AMD_EINVAL;
+    const int D = p.arch.D, W = p.arch.W;
+    hipLaunchKernelGGL(fold_kernel, dim3(W / 2), dim3(256), 0, s, d_w.p[D], d_b.p[D], d_w.p[D + 2], d_b.p[D + 2], W,
+                       p.input_ch_views, t.fold_w, t.fold_b);
+    d_w.p[p.fold_tensor] = t.fold_w;
+    d_b.p[p.fold_tensor] = t.fold_b;
+    return launch_jobs(stream_jobs(p, t, NERF_AMD_COPY_BF16_FOLD), d_w, d_b, s);
+}
+
+int launch_pack(const Program &p, const DevTables &t, const PtrTable &d_w, const PtrTable &d_b, int copies, hipStream_t s) {
+    PackJobs J = stream_jobs(p, t, copies & ~NERF_AMD_COPY_BF16_FOLD);
+    J.layers = t.d_layers; J.tlayers = t.d_tlayers;
+    J.stream_f32 = t.stream_f32; J.bias_f32 = t.bias_f32; J.stream_f32_t = t.stream_f32_t;
+    J.n_layers = (copies & NERF_AMD_COPY_FP32) ? (int)p.layers.size() : 0;
+    J.n_layers_t = (copies & NERF_AMD_COPY_FP32_BWD) && t.stream_f32_t ? (int)p.layers.size() : 0;
+    return launch_jobs(J, d_w, d_b, s);
+}
+
+void pack_bf16_host(const Program &p, StreamId id, const float *const *w, const float *const *b, uint16_t *stream, float *bias) {
+    const FragStream &fs = p.streams[id];
+    const TensorDesc *tensors = p.tensors.data();
+    std::vector<const float *> ww, bb;       // the tables extended by the FOLD tensor
+    std::vector<TensorDesc> td;
+    std::vector<float> fw, fb;
+    if (id == ST_S16_FOLD) {       // the FOLD tensor first, like fold_kernel
         if (p.fold_tensor < 0) return;
+        ww.assign(w, w + p.tensors.size());
+        bb.assign(b, b + p.tensors.size());
+        td = p.tensors;
         const int D = p.arch.D, W = p.arch.W, n_in = W + p.input_ch_views;
-        std::vector<float> fw((size_t)(W / 2) * n_in), fb(W / 2);
+        fw.resize((size_t)(W / 2) * n_in);
+        fb.resize(W / 2);
         for (int o = 0; o < W / 2; ++o) {
             const float *row = w[D + 2] + (int64_t)o * n_in;
             for (int i = 0; i < n_in; ++i) fw[(size_t)o * n_in + i] = i < W ? fold_dot(row, w[D] + i, W, W) : row[i];
             fb[o] = fold_dot(row, b[D], 1, W) + b[D + 2][o];
         }
-        std::vector<const float *> ww(w, w + p.tensors.size()), bb(b, b + p.tensors.size());
         ww.push_back(fw.data());
         bb.push_back(fb.data());
-        std::vector<TensorDesc> td(p.tensors);
         td.push_back({W / 2, n_in});
-        if (stream)
-            for (size_t n = 0; n < p.frags16_fold.size(); ++n)
-                for (int lane = 0; lane < 64; ++lane)
-                    for (int j = 0; j < 8; ++j) {
-                        int row;
-                        const FragDesc &d = p.frags16_fold[n];
-                        const TensorDesc &t = td[d.tensor];
-                        const int col = frag_source(d, lane, j, t.n_out, &row);
-                        stream[n * 512 + lane * 8 + j] = f32_to_bf16_rne(col < 0 ? 0.0f : ww[d.tensor][(int64_t)row * t.n_in + col]);
-                    }
-        if (bias)
-            for (size_t ti = 0; ti < p.tiles16_fold.size(); ++ti)
-                for (int r = 0; r < 16; ++r) {
-                    const TileDesc &t = p.tiles16_fold[ti];
-                    bias[ti * 16 + r] = t.row0 + r < td[t.tensor].n_out ? bb[t.tensor][t.row0 + r] : 0.0f;
-                }
-        return;
-    }
-    if (shape == 17) {       // backward (transposed) stream; no bias table
-        if (stream)
-            for (size_t n = 0; n < p.frags_bwd.size(); ++n)
-                for (int lane = 0; lane < 64; ++lane)
-                    for (int j = 0; j < 8; ++j) {
-                        int row;
-                        const TensorDesc &t = p.tensors[p.frags_bwd[n].tensor];
-                        const int col = frag_source(p.frags_bwd[n], lane, j, t.n_out, &row);
-                        stream[n * 512 + lane * 8 + j] =
-                            f32_to_bf16_rne(col < 0 ? 0.0f : w[p.frags_bwd[n].tensor][(int64_t)row * t.n_in + col]);
-                    }
-        return;
-    }
-    if (shape == 18 || shape == 19) {   // split-precision streams (fp16 hi / lo fragments): 18 forward (bias table = shape 16's), 19 transposed
-        const std::vector<FragDesc> &fr = shape == 18 ? p.frags_split : p.frags_bwd_split;
-        if (stream)
-            for (size_t n = 0; n < fr.size(); ++n)
-                for (int lane = 0; lane < 64; ++lane)
-                    for (int j = 0; j < 8; ++j) {
-                        int row;
-                        const FragDesc &d = fr[n];
-                        const TensorDesc &t = p.tensors[d.tensor];
-                        const int col = frag_source(d, lane, j, t.n_out, &row);
-                        stream[n * 512 + lane * 8 + j] = pack_value(col < 0 ? 0.0f : w[d.tensor][(int64_t)row * t.n_in + col], d.part);
-                    }
-        return;
-    }
-    if (shape == 16) {
-        if (stream)
-            for (size_t n = 0; n < p.frags16.size(); ++n)
-                for (int lane = 0; lane < 64; ++lane)
-                    for (int j = 0; j < 8; ++j) {
-                        int row;
-                        const TensorDesc &t = p.tensors[p.frags16[n].tensor];
-                        const int col = frag_source(p.frags16[n], lane, j, t.n_out, &row);
-                        stream[n * 512 + lane * 8 + j] =
-                            f32_to_bf16_rne(col < 0 ? 0.0f : w[p.frags16[n].tensor][(int64_t)row * t.n_in + col]);
-                    }
-        if (bias)
-            for (size_t ti = 0; ti < p.tiles16.size(); ++ti)
-                for (int r = 0; r < 16; ++r) {
-                    const int row = p.tiles16[ti].row0 + r;
-                    bias[ti * 16 + r] = row < p.tensors[p.tiles16[ti].tensor].n_out ? b[p.tiles16[ti].tensor][row] : 0.0f;
-                }
-        return;
+        w = ww.data(); b = bb.data(); tensors = td.data();
     }
     if (stream)
-        for (size_t n = 0; n < p.frags.size(); ++n)
-            for (int lane = 0; lane < 64; ++lane)
-                for (int j = 0; j < 8; ++j) {
-                    int row;
-                    const TensorDesc &t = p.tensors[p.frags[n].tensor];
-                    const int col = frag_source(p.frags[n], lane, j, t.n_out, &row);
-                    stream[n * 512 + lane * 8 + j] =
-                        f32_to_bf16_rne(col < 0 ? 0.0f : w[p.frags[n].tensor][(int64_t)row * t.n_in + col]);
-                }
+        for (size_t n = 0; n < fs.frags.size(); ++n)
+            for (int e = 0; e < 512; ++e) stream[n * 512 + e] = frag_value(fs.frags[n], e >> 3, e & 7, tensors, w);
+    const int rows = STREAMS[id].bias_rows;
     if (bias)
-        for (size_t ti = 0; ti < p.tiles.size(); ++ti)
-            for (int h = 0; h < 2; ++h)
-                for (int r = 0; r < 16; ++r) {
-                    const int row = p.tiles[ti].row0 + acc_row(r, h);
-                    bias[ti * 32 + h * 16 + r] = row < p.tensors[p.tiles[ti].tensor].n_out ? b[p.tiles[ti].tensor][row] : 0.0f;
-                }
+        for (size_t e = 0; e < fs.tiles.size() * rows; ++e) bias[e] = bias_value(fs.tiles.data(), rows, (int)e, tensors, b);
 }
 
 }  // namespace na

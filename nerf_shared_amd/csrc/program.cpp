@@ -7,6 +7,12 @@ namespace na {
 
 namespace {
 struct Seg { int kind, col_base, len, nk, L; };
+
+// The sequence is complete: note its length and zero-pad it to a whole number of ring turns.
+void finish_stream(FragStream &s) {
+    s.n_used = (int)s.frags.size();
+    while (s.frags.size() % STREAM_PAD_FRAGS) s.frags.push_back({0, FRAG_ZERO, 0, 0, 0, 0, 0, 0});
+}
 }
 
 int build_program(const nerf_amd_arch &a, Program &p, const char **err) {
@@ -114,15 +120,17 @@ int build_program(const nerf_amd_arch &a, Program &p, const char **err) {
     // ---- bf16 fused program: canonical D=8, W=256, skips=[4]
     p.bf16_ok = (D == 8 && W == 256 && a.n_skips == 1 && a.skips[0] == 4);
     if (p.bf16_ok) {
+        FragStream &s32 = p.streams[ST_BF16_32], &s16 = p.streams[ST_S16], &fold = p.streams[ST_S16_FOLD], &split = p.streams[ST_SPLIT],
+                   &bwd = p.streams[ST_BWD], &bwd_split = p.streams[ST_BWD_SPLIT];
         p.KE = gen_ksteps(Lx);
         p.KD = a.use_viewdirs ? gen_ksteps(Ld) : 0;
         auto add_layer = [&](int tensor, std::initializer_list<Seg> segs) {
             int n_out = p.tensors[tensor].n_out;
             for (int t = 0; t < (n_out + 31) / 32; ++t) {
-                p.tiles.push_back({tensor, 32 * t});
+                s32.tiles.push_back({tensor, 32 * t});
                 for (const Seg &s : segs)
                     for (int ks = 0; ks < s.nk; ++ks)
-                        p.frags.push_back({tensor, s.kind, 32 * t, s.col_base, ks, s.len, s.L, 0});
+                        s32.frags.push_back({tensor, s.kind, 32 * t, s.col_base, ks, s.len, s.L, 0});
             }
         };
         const Seg E{FRAG_GEN, 0, p.input_ch, p.KE, Lx};
@@ -140,8 +148,7 @@ int build_program(const nerf_amd_arch &a, Program &p, const char **err) {
         } else {
             add_layer(8, {H});                                                         // output_linear
         }
-        p.n_frags_used = (int)p.frags.size();
-        while (p.frags.size() % STREAM_PAD_FRAGS) p.frags.push_back({0, FRAG_ZERO, 0, 0, 0, 0, 0, 0});
+        finish_stream(s32);
 
         // ---- s16 program: layer -> pair of 16-row tiles -> k-step -> tile of the pair
         p.KE16 = gen16_ksteps(Lx);
@@ -151,14 +158,14 @@ int build_program(const nerf_amd_arch &a, Program &p, const char **err) {
             const int n_tiles = (n_out + 15) / 16;
             for (int t = 0; t < n_tiles; t += 2) {
                 const int in_pair = (t + 1 < n_tiles) ? 2 : 1;
-                for (int u = 0; u < in_pair; ++u) p.tiles16.push_back({tensor, 16 * (t + u)});
+                for (int u = 0; u < in_pair; ++u) s16.tiles.push_back({tensor, 16 * (t + u)});
                 for (const Seg &s : segs)
                     for (int ks = 0; ks < s.nk; ++ks) {
                         for (int u = 0; u < in_pair; ++u)
-                            p.frags16.push_back({tensor, s.kind, 16 * (t + u), s.col_base, ks, s.len, s.L, 0});
+                            s16.frags.push_back({tensor, s.kind, 16 * (t + u), s.col_base, ks, s.len, s.L, 0});
                         for (int part = 1; part <= 2; ++part)          // the same fragments as fp16 hi / lo parts
                             for (int u = 0; u < in_pair; ++u)
-                                p.frags_split.push_back({tensor, s.kind, 16 * (t + u), s.col_base, ks, s.len, s.L, part});
+                                split.frags.push_back({tensor, s.kind, 16 * (t + u), s.col_base, ks, s.len, s.L, part});
                     }
             }
         };
@@ -177,32 +184,29 @@ int build_program(const nerf_amd_arch &a, Program &p, const char **err) {
         } else {
             add_layer16(8, {H16});
         }
-        p.n_frags16_used = (int)p.frags16.size();
-        while (p.frags16.size() % STREAM_PAD_FRAGS) p.frags16.push_back({0, FRAG_ZERO, 0, 0, 0, 0, 0, 0});
+        finish_stream(s16);
         // ---- folded s16 program: the same order without layer 8 (feature); the views layer reads the FOLD tensor
         if (a.use_viewdirs) {
             p.fold_tensor = (int)p.tensors.size();
             size_t n_frag = 0, n_tile = 0;
-            auto copy_layer = [&](int tensor, int as_tensor) {          // a layer of frags16 / tiles16, re-labelled
-                for (; n_frag < (size_t)p.n_frags16_used && p.frags16[n_frag].tensor == tensor; ++n_frag) {
-                    FragDesc d = p.frags16[n_frag];
+            auto copy_layer = [&](int tensor, int as_tensor) {          // a layer of the s16 stream, re-labelled
+                for (; n_frag < (size_t)s16.n_used && s16.frags[n_frag].tensor == tensor; ++n_frag) {
+                    FragDesc d = s16.frags[n_frag];
                     d.tensor = as_tensor;
-                    p.frags16_fold.push_back(d);
+                    fold.frags.push_back(d);
                 }
-                for (; n_tile < p.tiles16.size() && p.tiles16[n_tile].tensor == tensor; ++n_tile)
-                    p.tiles16_fold.push_back({as_tensor, p.tiles16[n_tile].row0});
+                for (; n_tile < s16.tiles.size() && s16.tiles[n_tile].tensor == tensor; ++n_tile)
+                    fold.tiles.push_back({as_tensor, s16.tiles[n_tile].row0});
             };
             for (int i = 0; i < D; ++i) copy_layer(i, i);
-            while (n_frag < (size_t)p.n_frags16_used && p.frags16[n_frag].tensor == D) ++n_frag;      // feature: folded away
-            while (n_tile < p.tiles16.size() && p.tiles16[n_tile].tensor == D) ++n_tile;
+            while (n_frag < (size_t)s16.n_used && s16.frags[n_frag].tensor == D) ++n_frag;      // feature: folded away
+            while (n_tile < s16.tiles.size() && s16.tiles[n_tile].tensor == D) ++n_tile;
             copy_layer(D + 1, D + 1);                   // alpha
             copy_layer(D + 2, p.fold_tensor);           // views over [W' | Wv[:, W:]]: same shape as views_linears.0
             copy_layer(D + 3, D + 3);                   // rgb
-            p.n_frags16_fold_used = (int)p.frags16_fold.size();
-            while (p.frags16_fold.size() % STREAM_PAD_FRAGS) p.frags16_fold.push_back({0, FRAG_ZERO, 0, 0, 0, 0, 0, 0});
+            finish_stream(fold);
         }
-        p.n_frags_split_used = (int)p.frags_split.size();
-        while (p.frags_split.size() % STREAM_PAD_FRAGS) p.frags_split.push_back({0, FRAG_ZERO, 0, 0, 0, 0, 0, 0});
+        finish_stream(split);
 
         // ---- backward stream: g_in^T = W^T g_out^T, layer -> pair of 16-row input-feature tiles ->
         //      segment -> k-step -> tile of the pair (parameter gradients only: the encodings' own
@@ -214,11 +218,11 @@ int build_program(const nerf_amd_arch &a, Program &p, const char **err) {
                     for (const SegT &sg : segs)
                         for (int ks = 0; ks < sg.nk; ++ks) {
                             for (int u = 0; u < 2; ++u)
-                                p.frags_bwd.push_back({sg.tensor, sg.kind, 16 * (t + u), sg.col_base, ks,
+                                bwd.frags.push_back({sg.tensor, sg.kind, 16 * (t + u), sg.col_base, ks,
                                                        p.tensors[sg.tensor].n_out, n_in, 0});
                             for (int part = 1; part <= 2; ++part)
                                 for (int u = 0; u < 2; ++u)
-                                    p.frags_bwd_split.push_back({sg.tensor, sg.kind, 16 * (t + u), sg.col_base, ks,
+                                    bwd_split.frags.push_back({sg.tensor, sg.kind, 16 * (t + u), sg.col_base, ks,
                                                                  p.tensors[sg.tensor].n_out, n_in, part});
                         }
             };
@@ -227,10 +231,10 @@ int build_program(const nerf_amd_arch &a, Program &p, const char **err) {
                 for (int t = 0; t < n_slots / 16; t += 2)
                     for (int ks = 0; ks < nk; ++ks) {
                         for (int u = 0; u < 2; ++u)
-                            p.frags_bwd.push_back({tensor, FRAG_TE16, 16 * (t + u), col_base, ks, p.tensors[tensor].n_out, L, 0});
+                            bwd.frags.push_back({tensor, FRAG_TE16, 16 * (t + u), col_base, ks, p.tensors[tensor].n_out, L, 0});
                         for (int part = 1; part <= 2; ++part)
                             for (int u = 0; u < 2; ++u)
-                                p.frags_bwd_split.push_back({tensor, FRAG_TE16, 16 * (t + u), col_base, ks, p.tensors[tensor].n_out, L, part});
+                                bwd_split.frags.push_back({tensor, FRAG_TE16, 16 * (t + u), col_base, ks, p.tensors[tensor].n_out, L, part});
                     }
             };
             if (a.use_viewdirs) {
@@ -246,10 +250,8 @@ int build_program(const nerf_amd_arch &a, Program &p, const char **err) {
                 if (is_skip(l - 1)) add_bwd_enc(l, 0, 32 * p.KE16, Lx, W / 32);                // g_e    <- its [input_pts] columns
             }
             add_bwd_enc(0, 0, 32 * p.KE16, Lx, W / 32);                                        // g_e    <- pts_linears.0
-            p.n_frags_bwd_used = (int)p.frags_bwd.size();
-            while (p.frags_bwd.size() % STREAM_PAD_FRAGS) p.frags_bwd.push_back({0, FRAG_ZERO, 0, 0, 0, 0, 0, 0});
-            p.n_frags_bwd_split_used = (int)p.frags_bwd_split.size();
-            while (p.frags_bwd_split.size() % STREAM_PAD_FRAGS) p.frags_bwd_split.push_back({0, FRAG_ZERO, 0, 0, 0, 0, 0, 0});
+            finish_stream(bwd);
+            finish_stream(bwd_split);
         }
     }
     return 0;

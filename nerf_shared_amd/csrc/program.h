@@ -149,41 +149,66 @@ NA_HD constexpr inline int acc16_col(int ks, int q, int j) { return 32 * ks + 16
 
 inline int embed_dim(int L, int i_embed) { return i_embed == -1 ? 3 : 3 + 6 * L; }
 
-struct Program {
-    nerf_amd_arch arch;
-    int input_ch = 0, input_ch_views = 0, out_ch = 0;
-    std::vector<TensorDesc> tensors;
-    // bf16 fused program (empty when the architecture is not the canonical one)
-    bool bf16_ok = false;
-    int KE = 0, KD = 0;
-    std::vector<FragDesc> frags;     // padded to a whole number of ring turns
-    std::vector<TileDesc> tiles;
-    int n_frags_used = 0;
-    // bf16 s16 program (16x16x32 MFMA); tiles16 are 16-row tiles
-    int KE16 = 0, KD16 = 0;
-    std::vector<FragDesc> frags16;
-    std::vector<TileDesc> tiles16;
-    int n_frags16_used = 0;
+// The packed 1-KiB fragment streams of the fused family, one table from the program to the packers to the model's buffers.
+// A new stream is one enum value, one row of STREAMS, its fragment sequence in build_program and one MlpArgs field.
+enum StreamId {
+    ST_BF16_32,      // 32x32x16 bf16 (mlp_bf16.hip); bias tiles of 32 rows in acc_row order
+    ST_S16,          // 16x16x32 bf16 (mlp_bf16_s16.hip); bias tiles of 16 rows, shared with ST_SPLIT
     // folded s16 program (view-branch models; inference only): feature_linear has no activation behind it, so
     // views_linears.0 reads h8 through W' = Wv[:, :W] . Wf (and b' = Wv[:, :W] . bf + bv).  The s16 program without the
     // feature layer; the views layer is {H16 over W', GEN16 over Wv[:, W:]}, both read from the FOLD tensor: index
     // tensors.size() of the pack's tables, a per-model fp32 scratch [W/2][W + input_ch_views] (+ [W/2] bias) that
     // fold_kernel (pack.hip) fills from the fp32 parameters in front of the pack.  Empty without a view branch.
-    std::vector<FragDesc> frags16_fold;
-    std::vector<TileDesc> tiles16_fold;
-    int n_frags16_fold_used = 0;
-    int fold_tensor = -1;            // index of the FOLD tensor in the pack's tensor table, -1: nothing to fold
+    ST_S16_FOLD,
     // split-precision stream (mlp_split.hip): the s16 program with every fragment as an fp16 (hi, lo) pair, ordered
-    // layer -> pair of output tiles -> k-step -> part -> tile of the pair; the bias table is tiles16's
-    std::vector<FragDesc> frags_split;
-    int n_frags_split_used = 0;
-    // backward (transposed-weight) stream for the s16 kernel; view-branch (10,4) model only
-    std::vector<FragDesc> frags_bwd;
-    int n_frags_bwd_used = 0;
+    // layer -> pair of output tiles -> k-step -> part -> tile of the pair; no bias table of its own, it reads ST_S16's
+    ST_SPLIT,
+    ST_BWD,          // backward (transposed-weight) stream of mlp_bwd_s16.hip; no bias table
     // the same transposed stream as fp16 (hi, lo) pairs for the split-precision dX chain (mlp_bwd_split.hip): per pair of
-    // tiles and k-step four fragments hi(t0), hi(t1), lo(t0), lo(t1), like frags_split
-    std::vector<FragDesc> frags_bwd_split;
-    int n_frags_bwd_split_used = 0;
+    // tiles and k-step four fragments hi(t0), hi(t1), lo(t0), lo(t1), like ST_SPLIT
+    ST_BWD_SPLIT,
+    N_STREAMS
+};
+
+struct FragStream {
+    std::vector<FragDesc> frags;     // zero-padded to a multiple of STREAM_PAD_FRAGS (a whole number of ring turns)
+    int n_used = 0;                  // fragments in front of the padding
+    std::vector<TileDesc> tiles;     // the bias table the stream owns; empty for a stream without one
+};
+
+struct StreamInfo {
+    int shape;                       // shape code of nerf_amd_pack_bf16_host
+    const char *what;                // ... and its name in that entry point's error text
+    int copy;                        // NERF_AMD_COPY_* bit that packs the stream
+    int bias_rows;                   // rows of a bias tile: 0 none, 16 natural order, 32 in acc_row order
+    int bias_copy;                   // another bit that packs the bias table too (its other reader's)
+};
+constexpr StreamInfo STREAMS[N_STREAMS] = {
+    {32, "32x32x16 stream", NERF_AMD_COPY_BF16, 32, 0},
+    {16, "16x16x32 stream", NERF_AMD_COPY_BF16, 16, NERF_AMD_COPY_SPLIT},
+    {20, "folded 16x16x32 stream", NERF_AMD_COPY_BF16_FOLD, 16, 0},
+    {18, "split-precision stream", NERF_AMD_COPY_SPLIT, 0, 0},
+    {17, "backward stream", NERF_AMD_COPY_BWD, 0, 0},
+    {19, "split-precision backward stream", NERF_AMD_COPY_BWD_SPLIT, 0, 0},
+};
+constexpr int stream_of_shape(int shape) {      // StreamId, or -1
+    for (int i = 0; i < N_STREAMS; ++i)
+        if (STREAMS[i].shape == shape) return i;
+    return -1;
+}
+// Feature row (relative to the tile's row0) of element r of a bias tile of `rows` rows.
+NA_HD constexpr inline int bias_tile_row(int r, int rows) { return rows == 32 ? acc_row(r & 15, r >> 4) : r; }
+
+struct Program {
+    nerf_amd_arch arch;
+    int input_ch = 0, input_ch_views = 0, out_ch = 0;
+    std::vector<TensorDesc> tensors;
+    // bf16 fused programs (empty when the architecture is not the canonical one)
+    bool bf16_ok = false;
+    int KE = 0, KD = 0;              // k-steps of the encodings in ST_BF16_32
+    int KE16 = 0, KD16 = 0;          // ... and in the s16 streams
+    FragStream streams[N_STREAMS];
+    int fold_tensor = -1;            // index of the FOLD tensor in the pack's tensor table, -1: nothing to fold
     // fp32 generic program
     std::vector<LayerF32> layers;
     int64_t f32_stream_floats = 0, f32_bias_floats = 0;

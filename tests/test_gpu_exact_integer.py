@@ -177,9 +177,9 @@ def integer_rays(arch, R, S, seed):
 
 
 # ------------------------------------------------------------------------------------------------ float64 reference
-def net64(sd, arch, e_pts, e_dirs, tape=None):
+def net64(sd, arch, e_pts, e_dirs, tape=None, act=torch.relu):
     """NeRF.MLP (the reference's nerf.py:110-134) in float64 on encoded rows; `tape` collects (weight name, input,
-    pre-activation, has ReLU) of every layer."""
+    pre-activation, has ReLU) of every layer.  `act` stands in for the ReLU (partial_case: a recorded mask)."""
     A = _arch(arch)
 
     def lin(name, x, relu):
@@ -188,7 +188,7 @@ def net64(sd, arch, e_pts, e_dirs, tape=None):
             if z.requires_grad:
                 z.retain_grad()
             tape.append((name, x, z, relu))
-        return torch.relu(z) if relu else z
+        return act(z) if relu else z
 
     h = e_pts
     for i in range(A.D):
@@ -630,3 +630,196 @@ def test_two_evaluations_in_one_graph_sum_exactly(dev, name, precision):
     both = dict(ra, grads={k: ra["grads"][k] + rb["grads"][k] for k in ra["grads"]},
                 bf16_model={k: ra["bf16_model"][k] + rb["bf16_model"][k] for k in ra["bf16_model"]})
     assert_param_grads("%s %s two sets:" % (name, precision), named_grads(m), both, precision)
+
+
+# ================================================================================================ partial packs
+# nerf_amd_model_update_copies(copies, others_current = 1) packs the copies it is asked for and leaves every other copy
+# alone.  All copies are packed from weights A, one bit is re-packed from other weights, and the kernel that reads that
+# copy must give the other weights' reference while a kernel that reads another copy still gives A's.
+#   B: other weights, A's biases.  C: A's weights, other biases (the 16-row bias table is read by the bf16 and the split
+#   kernel, so either bit has to pack it).
+# A backward copy is read after a forward from the matching forward copy, which still holds A: the dX chain then runs B's
+# transposed weights over A's ReLU masks.  Its reference is the gradient of the network with B's weights whose ReLUs are
+# replaced by A's recorded masks ("mixed").
+PARTIAL = {"vd_10_4": ("BF16", "SPLIT", "FP32", "BWD", "BWD_SPLIT", "FP32_BWD", "BF16_FOLD"), "novd_out4": ("FP32", "FP32_BWD")}
+PARTIAL_RS = (11, 3)          # 33 points: two 16-column tiles and a ragged one
+# bit -> (precision of its consumer, precision of a consumer of another copy)
+PARTIAL_FORWARD = {"BF16": ("bf16", "fp32_split"), "SPLIT": ("fp32_split", "bf16"), "FP32": ("fp32", "bf16")}
+PARTIAL_BACKWARD = {"BWD": ("bf16", "fp32_split"), "BWD_SPLIT": ("fp32_split", "bf16"), "FP32_BWD": ("fp32", "bf16")}
+
+
+def abi_names(arch):
+    """Parameter tensors in the order of include/nerf_amd.h."""
+    heads = ["feature_linear", "alpha_linear", "views_linears.0", "rgb_linear"] if arch["use_viewdirs"] else ["output_linear"]
+    return ["pts_linears.%d" % i for i in range(arch["D"])] + heads
+
+
+def masked_input_grads(arch, sd_masks, sd, pts, vd, g_raw):
+    """(g_pts, g_viewdirs, largest |dL/d pre-activation|) in float64 of the network with weights `sd` whose ReLUs are the
+    masks that the network with weights `sd_masks` records at the same inputs."""
+    A = _arch(arch)
+
+    def encoded(p64, v64):
+        e_dirs = O.embed(v64[:, None].expand(p64.shape).reshape(-1, 3), A.multires_views, A.i_embed) if v64 is not None else None
+        return O.embed(p64.reshape(-1, 3), A.multires, A.i_embed), e_dirs
+
+    tape = []
+    with torch.no_grad():
+        net64({k: v.double() for k, v in sd_masks.items()}, arch, *encoded(pts.double(), vd.double() if vd is not None else None), tape)
+    masks = iter([(z > 0).double() for _, _, z, relu in tape if relu])
+    p64 = pts.double().requires_grad_(True)
+    v64 = vd.double().requires_grad_(True) if vd is not None else None
+    tape = []
+    raw = net64({k: v.double() for k, v in sd.items()}, arch, *encoded(p64, v64), tape, act=lambda z: z * next(masks))
+    (raw.reshape(g_raw.shape) * g_raw.double()).sum().backward()
+    return p64.grad.detach(), v64.grad.detach() if v64 is not None else None, max(float(z.grad.abs().max()) for _, _, z, _ in tape)
+
+
+def partial_case(name):
+    """Weights A, B, C, the inputs, the references of all three and the mixed dX references; computed once."""
+    key = ("partial", name)
+    if key not in _CACHE:
+        arch = ARCHS[name]
+        A = weights(name)
+        other = integer_state_dict(arch, 900 + WEIGHT_SEED[name])
+        B = {k: (A if k.endswith(".bias") else other)[k] for k in A}
+        C = {k: (other if k.endswith(".bias") else A)[k] for k in A}
+        pts, vd, g_raw = integer_inputs(arch, *PARTIAL_RS, 4242 + WEIGHT_SEED[name])
+        refs = {tag: reference(arch, sd, pts, vd, g_raw) for tag, sd in (("A", A), ("B", B), ("C", C))}
+        _CACHE[key] = (dict(A=A, B=B, C=C), pts, vd, g_raw, refs, masked_input_grads(arch, A, B, pts, vd, g_raw))
+    return _CACHE[key]
+
+
+@pytest.mark.parametrize("name", sorted(PARTIAL))
+def test_partial_pack_generator_meets_the_preconditions(name):
+    """Exactness is owed on all three weight sets and on the mixed dX chain; the three references differ from each other
+    (a kernel that read the wrong copy cannot pass); with the same weights on both sides the mixed chain is the plain one."""
+    arch = ARCHS[name]
+    sds, pts, vd, g_raw, refs, (g_pts, g_vd, max_dx) = partial_case(name)
+    assert pts.shape[0] * pts.shape[1] == 33
+    for tag, sd in sds.items():
+        assert all(is_integer(v) for v in sd.values())
+        for k, m in sincos_columns(arch).items():
+            assert float(sd[k][:, m].abs().max()) == 0.0, (tag, k)
+        check_exactness_owed(arch, refs[tag])
+    for n in abi_names(arch):
+        assert torch.equal(sds["A"][n + ".bias"], sds["B"][n + ".bias"]) and not torch.equal(sds["A"][n + ".weight"], sds["B"][n + ".weight"])
+        assert torch.equal(sds["A"][n + ".weight"], sds["C"][n + ".weight"])
+        if sds["A"][n + ".bias"].numel() >= 16:           # (a head of one or three rows may draw the same biases twice)
+            assert not torch.equal(sds["A"][n + ".bias"], sds["C"][n + ".bias"])
+    for a, b in (("A", "B"), ("A", "C"), ("B", "C")):
+        assert not torch.equal(refs[a]["raw"], refs[b]["raw"]), (a, b)
+    assert is_integer(g_pts) and max_dx <= 256 and (g_vd is None or is_integer(g_vd))
+    assert not torch.equal(g_pts, refs["A"]["g_pts"]) and not torch.equal(g_pts, refs["B"]["g_pts"])
+    same = masked_input_grads(arch, sds["A"], sds["A"], pts, vd, g_raw)
+    assert torch.equal(same[0], refs["A"]["g_pts"]) and (vd is None or torch.equal(same[1], refs["A"]["g_vd"]))
+    if arch["use_viewdirs"]:           # the folded stream of B and C: W' and b' are exact too (test_gpu_fold.py)
+        for tag in ("B", "C"):
+            wf, bf = sds[tag]["feature_linear.weight"].double(), sds[tag]["feature_linear.bias"].double()
+            wv, bv = sds[tag]["views_linears.0.weight"].double(), sds[tag]["views_linears.0.bias"].double()
+            w, b = wv[:, :arch["W"]] @ wf, wv[:, :arch["W"]] @ bf + bv
+            assert is_integer(w) and is_integer(b) and float(w.abs().max()) <= 256 and float(b.abs().max()) <= 256
+
+
+class PackedModel:
+    """A library model driven through the C ABI, so that the test decides which copy is packed from which weights."""
+
+    def __init__(self, dev, arch):
+        import ctypes
+        from nerf_shared_amd import _lib
+        self._lib, self.lib, self.dev, self.arch = _lib, _lib.lib, dev, arch
+        self.ch = 4 if arch["use_viewdirs"] else arch["output_ch"]
+        a = _lib.make_arch(arch["D"], arch["W"], arch["output_ch"], arch["skips"], arch["use_viewdirs"], arch["multires"],
+                           arch["multires_views"], 0)
+        self.h = ctypes.c_void_p()
+        _lib.check(self.lib.nerf_amd_model_create(ctypes.byref(a), dev.index or 0, ctypes.byref(self.h)), "nerf_amd_model_create")
+        self.stream = _lib.stream_of(dev)
+
+    def close(self):
+        torch.cuda.synchronize()
+        self.lib.nerf_amd_model_destroy(self.h)
+
+    def pack(self, sd, copies, others_current):
+        import ctypes
+        names = abi_names(self.arch)
+        live = [sd[n + ".weight"].to(self.dev).contiguous() for n in names] + [sd[n + ".bias"].to(self.dev).contiguous() for n in names]
+        n = len(names)
+        wp = (ctypes.c_void_p * n)(*[t.data_ptr() for t in live[:n]])
+        bp = (ctypes.c_void_p * n)(*[t.data_ptr() for t in live[n:]])
+        self._lib.check(self.lib.nerf_amd_model_update_copies(self.h, wp, bp, n, copies, others_current, self.stream), "update_copies")
+        torch.cuda.synchronize()          # (the parameter tensors die with this call)
+
+    def forward(self, precision, pts, vd):
+        R, S = pts.shape[:2]
+        p, v = pts.to(self.dev).reshape(-1, 3).contiguous(), vd.to(self.dev).contiguous() if vd is not None else None
+        out = torch.empty(R * S, self.ch, device=self.dev)
+        self._lib.check(self.lib.nerf_amd_nerf_forward(self.h, p.data_ptr(), self._lib.ptr(v), R, S, out.data_ptr(), self.prec(precision),
+                                                       self.stream), "nerf_amd_nerf_forward")
+        torch.cuda.synchronize()
+        return out.reshape(R, S, self.ch)
+
+    def prec(self, precision):
+        return {"bf16": self._lib.PREC_BF16, "fp32_split": self._lib.PREC_FP32_SPLIT, "fp32": self._lib.PREC_FP32}[precision]
+
+    def forward_backward_inputs(self, precision, pts, vd, g_raw):
+        """(raw, g_pts, g_viewdirs) of nerf_amd_field_forward_train followed by nerf_amd_field_backward_inputs."""
+        R, S = pts.shape[:2]
+        prec = self.prec(precision)
+        p, v = pts.to(self.dev).reshape(-1, 3).contiguous(), vd.to(self.dev).contiguous() if vd is not None else None
+        g = g_raw.to(self.dev).reshape(R * S, self.ch).contiguous()
+        ws = torch.empty(max(self.lib.nerf_amd_train_workspace(self.h, R * S, prec), 1), dtype=torch.uint8, device=self.dev)
+        raw, g_pts = torch.empty(R * S, self.ch, device=self.dev), torch.empty(R * S, 3, device=self.dev)
+        g_vd = torch.zeros(R, 3, device=self.dev) if v is not None else None
+        self._lib.check(self.lib.nerf_amd_field_forward_train(self.h, p.data_ptr(), self._lib.ptr(v), None, 0, None, R, S, raw.data_ptr(),
+                                                              ws.data_ptr(), ws.numel(), prec, self.stream), "nerf_amd_field_forward_train")
+        self._lib.check(self.lib.nerf_amd_field_backward_inputs(self.h, g.data_ptr(), p.data_ptr(), self._lib.ptr(v), None, 0, None, R, S,
+                                                                ws.data_ptr(), ws.numel(), g_pts.data_ptr(), None, self._lib.ptr(g_vd), prec,
+                                                                self.stream), "nerf_amd_field_backward_inputs")
+        torch.cuda.synchronize()
+        return raw.reshape(R, S, self.ch), g_pts.reshape(R, S, 3), g_vd
+
+
+@gpu
+@pytest.mark.parametrize("name", sorted(PARTIAL))
+def test_a_partial_pack_packs_what_is_asked_for_and_nothing_else(dev, name):
+    """Every copy from A, then one NERF_AMD_COPY_* bit from B with others_current = 1: the copy's consumer gives B's
+    reference (a backward copy: the mixed one) and a consumer of another copy still gives A's, both bit for bit.  Then the
+    16-row bias table: packing the split copy alone, or the bf16 copy alone, from C carries C's biases into that kernel."""
+    from nerf_shared_amd import _lib
+    sds, pts, vd, g_raw, refs, (mixed_g_pts, mixed_g_vd, _) = partial_case(name)
+    everything = _lib.COPY_ALL | (_lib.COPY_BF16_FOLD if ARCHS[name]["use_viewdirs"] else 0)
+    m = PackedModel(dev, ARCHS[name])
+    try:
+        for bit in PARTIAL[name]:
+            tag = "%s, %s from B:" % (name, bit)
+            m.pack(sds["A"], everything, 0)
+            m.pack(sds["B"], getattr(_lib, "COPY_" + bit), 1)
+            if bit in PARTIAL_FORWARD:
+                mine, other = PARTIAL_FORWARD[bit]
+                assert_exact("%s %s raw" % (tag, mine), m.forward(mine, pts, vd), refs["B"]["raw"])
+                assert_exact("%s %s raw (another copy)" % (tag, other), m.forward(other, pts, vd), refs["A"]["raw"])
+            elif bit in PARTIAL_BACKWARD:
+                mine, other = PARTIAL_BACKWARD[bit]
+                raw, g_pts, g_vd = m.forward_backward_inputs(mine, pts, vd, g_raw)
+                assert_exact("%s %s raw (the forward copy)" % (tag, mine), raw, refs["A"]["raw"])
+                assert_exact("%s %s g_pts" % (tag, mine), g_pts, mixed_g_pts)
+                if vd is not None:
+                    assert_exact("%s %s g_viewdirs" % (tag, mine), g_vd, mixed_g_vd)
+                raw, g_pts, g_vd = m.forward_backward_inputs(other, pts, vd, g_raw)
+                assert_exact("%s %s g_pts (another copy)" % (tag, other), g_pts, refs["A"]["g_pts"])
+                if vd is not None:
+                    assert_exact("%s %s g_viewdirs (another copy)" % (tag, other), g_vd, refs["A"]["g_vd"])
+            else:                        # the folded stream: nerf_amd_nerf_forward reads it under tuning key 2 = 2
+                assert_exact("%s unfolded bf16 raw (another copy)" % tag, m.forward("bf16", pts, vd), refs["A"]["raw"])
+                try:
+                    _lib.check(_lib.lib.nerf_amd_set_tuning(2, 2), "set_tuning")
+                    assert_exact("%s folded bf16 raw" % tag, m.forward("bf16", pts, vd), refs["B"]["raw"])
+                finally:
+                    _lib.lib.nerf_amd_set_tuning(2, 0)
+        if name in FUSED and "BF16" in PARTIAL[name]:
+            for bit, precision in (("SPLIT", "fp32_split"), ("BF16", "bf16")):
+                m.pack(sds["A"], everything, 0)
+                m.pack(sds["C"], getattr(_lib, "COPY_" + bit), 1)
+                assert_exact("%s, %s from C: %s raw" % (name, bit, precision), m.forward(precision, pts, vd), refs["C"]["raw"])
+    finally:
+        m.close()

@@ -1,4 +1,4 @@
-"""feature_linear folded into views_linears.0 in the bf16 render kernels (csrc/program.h frags16_fold, NERF_AMD_COPY_BF16_FOLD,
+"""feature_linear folded into views_linears.0 in the bf16 render kernels (csrc/program.h ST_S16_FOLD, NERF_AMD_COPY_BF16_FOLD,
 nerf_amd_set_tuning key 2).
 
 The reference network has no activation between feature_linear and views_linears.0 (nerf.py:110-134), so
@@ -77,7 +77,7 @@ def test_integer_weights_fold_exactly(name):
 
 def s16_program(arch, fold):
     """Python twin of csrc/program.cpp's s16 order (layer -> pair of 16-row tiles -> segment -> k-step -> tile of the pair):
-    [(tensor name, kind, row0, col_base, ks, seg_len, L)] and the bias tiles [(tensor name, row0)].  fold: frags16_fold."""
+    [(tensor name, kind, row0, col_base, ks, seg_len, L)] and the bias tiles [(tensor name, row0)].  fold: the ST_S16_FOLD stream."""
     A = X._arch(arch)
     W, ic, icv = A.W, A.input_ch, A.input_ch_views
     KE, KD = L.gen16_ksteps(A.multires), L.gen16_ksteps(A.multires_views)
@@ -144,7 +144,7 @@ def host_pack(arch, sd, shape):
 
 @pytest.mark.parametrize("name,integer", [("vd_10_4", True), ("vd_15_6", True), ("vd_10_4", False), ("vd_15_6", False)])
 def test_host_packer_folded_stream(name, integer):
-    """The host packer's folded stream (shape 20) holds bf16(W') and bf16(Wv[:, W:]) in the slots frags16_fold names, every
+    """The host packer's folded stream (shape 20) holds bf16(W') and bf16(Wv[:, W:]) in the slots ST_S16_FOLD names, every
     other layer's fragments where the unfolded stream has them minus the feature layer, zero padding to 192, and the bias
     table b' in the views tiles; the unfolded stream (shape 16) is what it was.  Integer weights: W' is exact.  Random weights:
     the packer sums k ascending in fp32, numpy in float64 -- the bf16 values may differ by one rounding step where W' sits

@@ -9,6 +9,9 @@ evaluation of the same weights, the permutations baked into the stream are
 consistent with the kernel's register layout.
 """
 import ctypes
+import hashlib
+import json
+import os
 
 import numpy as np
 import pytest
@@ -50,7 +53,8 @@ def gen_ksteps(L):
     return (3 * L + 2 + 7) // 8
 
 
-def host_pack(arch_kwargs, sd, shape=32):
+def host_pack_raw(arch_kwargs, sd, shape):
+    """(stream [n_frags * 512] uint16 with its zero padding, bias table [n_bias] float32) as the host packer writes them."""
     names = ["pts_linears.%d" % i for i in range(arch_kwargs["D"])]
     if arch_kwargs["use_viewdirs"]:
         names += ["feature_linear", "alpha_linear", "views_linears.0", "rgb_linear"]
@@ -70,6 +74,12 @@ def host_pack(arch_kwargs, sd, shape=32):
     _lib.check(lib.nerf_amd_pack_bf16_host(ctypes.byref(arch), shape, wp, bp, n,
                                            stream.ctypes.data_as(ctypes.POINTER(ctypes.c_uint16)), ctypes.byref(nf),
                                            bias.ctypes.data_as(ctypes.POINTER(ctypes.c_float)), ctypes.byref(nb)), "pack")
+    return stream, bias
+
+
+def host_pack(arch_kwargs, sd, shape=32):
+    stream, bias = host_pack_raw(arch_kwargs, sd, shape)
+    nf = ctypes.c_int64(stream.size // 512)
     if shape == 16:
         return bf16_bits_to_f32(stream).reshape(nf.value, 64, 8), bias.reshape(-1, 16)
     return bf16_bits_to_f32(stream).reshape(nf.value, 64, 8), bias.reshape(-1, 2, 16)
@@ -708,3 +718,34 @@ def test_backward_split_stream_is_the_backward_stream_as_fp16_pairs(arch):
             o = 16 * (j >> 2) + 4 * (l >> 4) + (j & 3)                             # acc16_col(ks = 0, q, j): output feature
             wv = np.float64(W[o, l & 15])                                          # element = W[o][input feature row0 + (l & 15)]
             assert abs(hi[l, j] + lo[l, j] / 2048.0 - wv) <= 2.0 ** -21 * abs(wv) + 2.0 ** -25, (l, j)
+
+
+# ---------------------------------------------------------------- every packed stream, byte for byte
+PACK_SHAPES = (32, 16, 17, 18, 19, 20)        # shape codes of nerf_amd_pack_bf16_host; 20 (folded) needs a view branch
+PACK_STREAMS_JSON = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "pack_streams.json")
+
+
+def pack_stream_cases():
+    """[(architecture name, architecture, shape code)] of tests/golden/pack_streams.json: the file carries the architectures it
+    was recorded for (the fused 8 x 256 family of tests/test_gpu_exact_integer.py, put there by make_pack_streams.py)."""
+    with open(PACK_STREAMS_JSON) as f:
+        archs = json.load(f)["architectures"]
+    return [(n, a, s) for n, a in sorted(archs.items()) for s in PACK_SHAPES if s != 20 or a["use_viewdirs"]]
+
+
+def pack_stream_digest(arch, shape):
+    """What tests/golden/pack_streams.json records of one stream: the sizes and a SHA-256 of the stream bytes (zero padding
+    included) and of the bias bytes, on non-integer weights (synth.make_state_dict, seed 3, x3)."""
+    sd = synth.make_state_dict(3, 3.0, **{**arch, "skips": tuple(arch["skips"])})
+    stream, bias = host_pack_raw(arch, sd, shape)
+    return dict(n_frags=stream.size // 512, n_bias=bias.size, stream_sha256=hashlib.sha256(stream.tobytes()).hexdigest(),
+                bias_sha256=hashlib.sha256(bias.tobytes()).hexdigest())
+
+
+@pytest.mark.parametrize("name,arch,shape", pack_stream_cases(), ids=["%s-%d" % (n, s) for n, _, s in pack_stream_cases()])
+def test_streams_are_the_recorded_bytes(name, arch, shape):
+    """The host packer's output against the digests tests/golden/make_pack_streams.py recorded (the file names the commit
+    whose library wrote them): a change to the program tables or the packer that moves one byte of one stream fails here."""
+    with open(PACK_STREAMS_JSON) as f:
+        want = json.load(f)["streams"]["%s-%d" % (name, shape)]
+    assert pack_stream_digest(arch, shape) == want
