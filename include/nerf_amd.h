@@ -605,6 +605,32 @@ int nerf_amd_occupancy_gather_rows(const float *dense, const int32_t *src, int64
 int nerf_amd_occupancy_ray_grads(const int32_t *rank, const float *z, const float *g_pts_live, const float *g_vd_live, int64_t R,
                                  int32_t S, int32_t ray_ch, float *g_rays, void *stream);
 
+/* Ray bounds: each ray's near / far (columns 6, 7 of rays [R, 8|11]) clipped to the span over which the grid is live
+ * along it, so that a sampler that reads near / far per ray puts its samples where the scene is.  probes = P is a power
+ * of two in 64..4096, 0 <= pad <= P, R < 2^31.  Per ray, with near = rays[r,6], far = rays[r,7], in fp32 operations
+ * rounded one by one:
+ *   w = far - near;   probe k (0 <= k < P) sits at t_k = near + w * u_k, u_k = (k + 0.5) / P (exact), the product
+ *   rounded, then the sum;  its point is rays_o + rays_d t_k, the product rounded first (the two operations of
+ *   nerf_amd_occupancy_cull);  it is LIVE by the lookup and the outside policy above (a NaN point is outside).
+ *   first = the smallest, last = the largest live k.
+ *   No live probe (a MISS):  span = (-1, -1), (near', far') = (near, far), the input bits.
+ *   Otherwise span = (first, last), k0 = max(first - pad, 0), k1 = min(last + pad, P - 1),
+ *     near' = near (the input bits) when k0 == 0,     else near + w * (k0 / P),
+ *     far'  = far  (the input bits) when k1 == P - 1, else near + w * ((k1 + 1) / P)      (k / P is exact).
+ * Outputs, each optional (NULL) but at least one given:  rays_out [R, ray_ch], distinct from rays: row r of rays with
+ * columns 6, 7 replaced by near', far', every other column copied;  bounds [R, 2] = (near', far');  span [R, 2] int32.
+ * R == 0 returns NERF_AMD_OK and launches nothing.  One 64-lane wave per ray, 64 probes a round, the round's live mask
+ * by ballot; no atomics, enqueue-only (it can be captured; the grid's words are read when it runs).
+ * PROMISED:  near <= near' <= far' <= far whenever near <= far and far - near are finite.  The result does not depend
+ *   on how many rounds the kernel skips.  For a CONVEX live set and pad >= 1 no point of [near, far] that looks up live
+ *   is left out, up to the rounding of the lookup: the live stretch is one interval, it is either shorter than a probe
+ *   spacing w / P (see below) or its ends lie within one spacing of first and last, which pad >= 1 covers.
+ * NOT PROMISED:  a live stretch shorter than one probe spacing w / P that lies beyond the outermost probed-live stretch
+ *   (or is the only one: the ray then counts as a miss) can be left out.  Gaps between first and last are kept: the
+ *   culls remove them.  Clipping is NOT idempotent: a second clip probes the narrowed interval and narrows it again. */
+int nerf_amd_occupancy_ray_bounds(const nerf_amd_occupancy_grid *grid, const float *rays, int32_t ray_ch, int64_t R,
+                                  int32_t probes, int32_t pad, float *rays_out, float *bounds, int32_t *span, void *stream);
+
 /* The field at a point list: pts [n,3], viewdirs [n,3] (one per POINT; NULL for a model without view branch) -> raw [n,ch].
  * Unlike nerf_amd_nerf_forward it takes the RENDER path's choice of weight stream (tuning key 2: the folded stream of a
  * bf16 view-branch model when NERF_AMD_COPY_BF16_FOLD is current), so a compacted pass runs the kernel the dense pass

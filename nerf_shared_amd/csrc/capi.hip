@@ -1079,6 +1079,18 @@ int nerf_amd_occupancy_ray_grads(const int32_t *rank, const float *z, const floa
     return rc ? fail(rc, "occupancy_ray_grads launch failed") : NERF_AMD_OK;
 }
 
+int nerf_amd_occupancy_ray_bounds(const nerf_amd_occupancy_grid *grid, const float *rays, int32_t ray_ch, int64_t R,
+                                  int32_t probes, int32_t pad, float *rays_out, float *bounds, int32_t *span, void *stream) {
+    OccGrid g;
+    if (int rc = occ_grid(grid, true, &g)) return rc;
+    if (R < 0 || R >= ((int64_t)1 << 31) || (ray_ch != 8 && ray_ch != 11) || probes < 64 || probes > 4096 || (probes & (probes - 1)) ||
+        pad < 0 || pad > probes || (!rays_out && !bounds && !span) || (R > 0 && !rays) || (rays_out && rays_out == rays))
+        return fail(NERF_AMD_EINVAL, "bad occupancy_ray_bounds arguments (probes: a power of two in 64..4096; 0 <= pad <= probes; "
+                                     "at least one output; rays_out distinct from rays)");
+    int rc = launch_occupancy_ray_bounds(g, rays, ray_ch, R, probes, pad, rays_out, bounds, span, static_cast<hipStream_t>(stream));
+    return rc ? fail(rc, "occupancy_ray_bounds launch failed") : NERF_AMD_OK;
+}
+
 int nerf_amd_field_points(const nerf_amd_model *m, const float *pts, const float *viewdirs, int64_t n, float *raw,
                           int precision, void *stream) {
     if (!m || n < 0) return fail(NERF_AMD_EINVAL, "bad field_points arguments");

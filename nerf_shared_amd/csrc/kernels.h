@@ -253,5 +253,8 @@ int launch_occupancy_cull_capped(const OccGrid &g, const float *rays, int ray_ch
 int launch_occupancy_gather_rows(const float *dense, const int32_t *src, int64_t capacity, int ch, float *live, hipStream_t s);
 int launch_occupancy_ray_grads(const int32_t *rank, const float *z, const float *g_pts, const float *g_vd, int64_t R, int S, int ray_ch,
                                float *g_rays, hipStream_t s);
+// each ray's near / far clipped to the span over which `probes` probes of it are live; any of the three outputs may be null
+int launch_occupancy_ray_bounds(const OccGrid &g, const float *rays, int ray_ch, int64_t R, int probes, int pad, float *rays_out,
+                                float *bounds, int32_t *span, hipStream_t s);
 
 }  // namespace na

@@ -395,4 +395,70 @@ int launch_occupancy_ray_grads(const int32_t *rank, const float *z, const float 
     return launched();
 }
 
+// ---------------------------------------------------------------------------
+// Ray bounds: each ray's [near, far] clipped to the span over which P probes of it look up live.  One 64-lane wave per ray
+// (four rays per block, like occupancy_ray_grads_kernel).  A round is 64 consecutive probes,
+// one per lane, and its ballot the round's live mask: rounds are walked forward to the first non-zero mask, then backward
+// from the end no further than that round (whose mask is kept).  The masks are wave-uniform, so are the loops, and an
+// early exit skips only rounds that cannot hold the first / last live probe.  No LDS, no atomics; lanes 0 .. ray_ch - 1
+// copy or replace the row.
+// ---------------------------------------------------------------------------
+__device__ __forceinline__ uint64_t probe_round(const OccGrid &g, const float o[3], const float d[3], float near, float w, int k, float inv_p) {
+    const float u = ((float)k + 0.5f) * inv_p;                         // exact: P is a power of two
+    const float t = mul_then_add(w, u, near);                         // near + w u, the product rounded first
+    const float px = mul_then_add(d[0], t, o[0]), py = mul_then_add(d[1], t, o[1]), pz = mul_then_add(d[2], t, o[2]);
+    return __ballot(live_at(g, cell_of(g, px, py, pz)));
+}
+
+__global__ __launch_bounds__(OC_BLOCK) void occupancy_ray_bounds_kernel(OccGrid g, const float *rays, int ray_ch, int64_t R, int P, int pad,
+                                                                        float *rays_out, float *bounds, int32_t *span) {
+    const int lane = threadIdx.x & 63;
+    const int rounds = P >> 6;
+    const float inv_p = 1.0f / (float)P;                              // exact
+    const int64_t ray = (int64_t)blockIdx.x * (OC_BLOCK / 64) + (threadIdx.x >> 6);
+    if (ray >= R) return;                                             // (whole waves leave: the ballots below see all 64 lanes)
+    {
+        const float *r = rays + ray * ray_ch;
+        const float o[3] = {r[0], r[1], r[2]}, d[3] = {r[3], r[4], r[5]};
+        const float near = r[6], far = r[7];
+        const float w = far - near;
+        int first = -1, last = -1, first_round = 0;
+        uint64_t m = 0;
+        for (int q = 0; q < rounds; ++q) {
+            m = probe_round(g, o, d, near, w, q * 64 + lane, inv_p);
+            if (m) {
+                first_round = q;
+                first = q * 64 + __builtin_ctzll(m);
+                break;
+            }
+        }
+        float near2 = near, far2 = far;
+        if (first >= 0) {
+            for (int q = rounds - 1; q >= first_round; --q) {
+                const uint64_t mq = q == first_round ? m : probe_round(g, o, d, near, w, q * 64 + lane, inv_p);
+                if (mq) {
+                    last = q * 64 + 63 - __builtin_clzll(mq);
+                    break;
+                }
+            }
+            const int k0 = max(first - pad, 0), k1 = min(last + pad, P - 1);
+            if (k0 > 0) near2 = mul_then_add(w, (float)k0 * inv_p, near);
+            if (k1 < P - 1) far2 = mul_then_add(w, (float)(k1 + 1) * inv_p, near);
+        }
+        if (rays_out && lane < ray_ch) rays_out[ray * ray_ch + lane] = lane == 6 ? near2 : lane == 7 ? far2 : r[lane];
+        if (lane < 2) {
+            if (bounds) bounds[2 * ray + lane] = lane == 0 ? near2 : far2;
+            if (span) span[2 * ray + lane] = lane == 0 ? first : last;
+        }
+    }
+}
+
+int launch_occupancy_ray_bounds(const OccGrid &g, const float *rays, int ray_ch, int64_t R, int probes, int pad, float *rays_out,
+                                float *bounds, int32_t *span, hipStream_t s) {
+    if (R <= 0) return NERF_AMD_OK;
+    hipLaunchKernelGGL(occupancy_ray_bounds_kernel, dim3(blocks_for(R * 64)), dim3(OC_BLOCK), 0, s, g, rays, ray_ch, R, probes, pad, rays_out,
+                       bounds, span);
+    return launched();
+}
+
 }  // namespace na

@@ -11,6 +11,9 @@ That culls the no-grad render calls.  Training and pose estimation cull through 
 (renderer.train_occupancy = TrainCull(grid)): compact lists of fixed capacity, nothing synchronises, the step still captures;
 OccupancyGrid.refresh_from_density keeps the grid following the models in place.
 
+renderer.ray_bounds = RayBounds(grid) moves the samples instead of removing them: every render call first clips each ray's
+near / far to the span over which the grid is live along it.
+
 Every operation is a HIP kernel of csrc/occupancy.hip with an exactly defined result; there is no CPU path.
 """
 import ctypes
@@ -133,6 +136,40 @@ class OccupancyGrid:
                                                             _lib.stream_of(self.device)), "nerf_amd_occupancy_sample_points")
         return pts
 
+    def _ray_bounds(self, rays, probes, pad, want_rays, want_bounds, want_span):
+        """nerf_amd_occupancy_ray_bounds on contiguous fp32 rays [R, 8|11] of this device -> (rays_out, bounds, span), None
+        where not asked for.  Enqueue-only."""
+        R, dev = rays.shape[0], self.device
+        rays_out = torch.empty_like(rays) if want_rays else None
+        bounds = torch.empty(R, 2, dtype=torch.float32, device=dev) if want_bounds else None
+        span = torch.empty(R, 2, dtype=torch.int32, device=dev) if want_span else None
+        g = self._c()
+        with torch.cuda.device(dev):
+            _lib.check(lib.nerf_amd_occupancy_ray_bounds(ctypes.byref(g), rays.data_ptr(), rays.shape[1], R, int(probes), int(pad),
+                                                         _lib.ptr(rays_out), _lib.ptr(bounds), _lib.ptr(span), _lib.stream_of(dev)),
+                       "nerf_amd_occupancy_ray_bounds")
+        return rays_out, bounds, span
+
+    def _check_rays(self, rays, name="rays"):
+        _lib.require_device(rays, name)
+        if rays.device != self.device:
+            raise _lib.NerfAmdError("%s is on %s, the grid on %s" % (name, rays.device, self.device))
+        if rays.dim() != 2 or rays.shape[1] not in (8, 11):
+            raise _lib.NerfAmdError("%s must be [N, 8] or [N, 11], got %s" % (name, tuple(rays.shape)))
+
+    def _rays(self, rays, name="rays"):
+        self._check_rays(rays, name)
+        return rays.detach().contiguous().float()
+
+    def ray_bounds(self, rays, probes=256, pad=1):
+        """rays [R, 8|11] -> (bounds [R, 2] float32, span [R, 2] int32): each ray's near / far (columns 6, 7) clipped to the
+        span over which `probes` equally spaced probes of it are live, widened by `pad` probe spacings, and the first and
+        last live probe ((-1, -1) and the ray's own near / far for a ray with none): nerf_amd_occupancy_ray_bounds.
+        probes: a power of two in 64..4096; 0 <= pad <= probes.  Never tracks gradients; nothing synchronises."""
+        probes, pad = _probes_pad(probes, pad)
+        _, bounds, span = self._ray_bounds(self._rays(rays), probes, pad, False, True, True)
+        return bounds, span
+
     def mask(self):
         """The grid as bool [nx, ny, nz] (a copy)."""
         shifts = torch.arange(32, dtype=torch.int32, device=self.device)
@@ -235,6 +272,64 @@ class OccupancyGrid:
         per = (self.n_words + m - 1) // m * 32
         c0 = min((i % m) * per, self.n_cells)
         return c0, min(c0 + per, self.n_cells)
+
+
+MIN_PROBES, MAX_PROBES = 64, 4096
+
+
+def _probes_pad(probes, pad):
+    """The two as ints, or ValueError: probes a power of two in 64..4096, 0 <= pad <= probes."""
+    if isinstance(probes, bool) or not isinstance(probes, int) or not (MIN_PROBES <= probes <= MAX_PROBES) or probes & (probes - 1):
+        raise ValueError("probes must be a power of two in %d..%d (got %r)" % (MIN_PROBES, MAX_PROBES, probes))
+    if isinstance(pad, bool) or not isinstance(pad, int) or not (0 <= pad <= probes):
+        raise ValueError("pad must be an int in 0..probes (got %r)" % (pad,))
+    return probes, pad
+
+
+class RayBounds:
+    """Clips each ray's near / far to the span over which the grid is live along it (set it as Renderer.ray_bounds): all
+    N_samples coarse samples, and the fine samples drawn from them, then lie where the scene is.  Every public render entry
+    applies it exactly once per call, to the batch as a whole, before its chunk loop and before any draw; it composes with
+    Renderer.occupancy and Renderer.train_occupancy (which still remove the gaps inside the span; the grids may differ).
+    The kernel is enqueue-only and reads the grid's words when it runs, so a captured step contains it and follows
+    OccupancyGrid.refresh_from_density.  Clipping is not idempotent -- a second clip probes the narrowed interval -- so do
+    not apply it to a batch that a renderer will clip again.  Building one touches no device.
+
+    TRAINING needs a wide pad.  The default pad = 1 is meant for rendering a trained model (measured: no loss).  Training
+    the sphere scene of tools/train_demo.py with it -- and with pad 8 -- ended 2.4 dB below the dense run; at pad 32 of 256
+    probes it ended level with it (profiles/occupancy_bounds.json).  tools/train_demo.py trains at 32."""
+
+    def __init__(self, grid, probes=256, pad=1):
+        if not isinstance(grid, OccupancyGrid):
+            raise TypeError("grid must be an OccupancyGrid (got %s)" % type(grid).__name__)
+        self.grid = grid
+        self.probes, self.pad = _probes_pad(probes, pad)
+
+    def apply(self, rays):
+        """rays [R, 8|11] -> the batch with columns 6, 7 clipped (fp32, contiguous).  For a batch that requires grad the
+        result carries the gradient of every other column back; the bounds are constants of the step (columns 6, 7 get +0.0),
+        as z_samples.detach() is in the reference."""
+        if rays.is_cuda and rays.device != self.grid.device:
+            raise _lib.NerfAmdError("Renderer.ray_bounds is on %s, the rays on %s" % (self.grid.device, rays.device))
+        if torch.is_grad_enabled() and rays.requires_grad:
+            self.grid._check_rays(rays)                                # (the conversion below is autograd's)
+            return _RayBoundsFn.apply(rays.contiguous().float(), self)
+        return self.grid._ray_bounds(self.grid._rays(rays), self.probes, self.pad, True, False, False)[0]
+
+
+class _RayBoundsFn(torch.autograd.Function):
+    """nerf_amd_occupancy_ray_bounds on the detached batch (contiguous fp32: RayBounds.apply converts, so that autograd
+    handles the dtype); the backward passes the gradient on with columns 6, 7 = +0.0."""
+
+    @staticmethod
+    def forward(ctx, rays, rb):
+        return rb.grid._ray_bounds(rays.detach(), rb.probes, rb.pad, True, False, False)[0]
+
+    @staticmethod
+    def backward(ctx, g):
+        g = g.clone()
+        g[:, 6:8] = 0.0
+        return g, None
 
 
 def _capacity(fraction, n):

@@ -328,6 +328,20 @@ class Renderer(torch.nn.Module):
                                                          net._precision_code(), _lib.stream_of(dev)), "nerf_amd_field_points")
         return occ._ExpandFn.apply(raw_live, rank, src).reshape(R, S, raw_live.shape[1])
 
+    # ------------------------------------------------------------------ ray bounds (opt-in)
+    ray_bounds = None             # a nerf_shared_amd.occupancy.RayBounds: render_rays and render_batch (and so every entry
+                                  # built on them) first clip each ray's near / far to the span over which its grid is live --
+                                  # once per call, on the batch as a whole, before the chunk loop and before any draw.  None:
+                                  # the batch goes on as it came, launch for launch.
+
+    def _clip(self, ray_batch):
+        """The batch a public entry goes on with: clipped by ray_bounds when one is set."""
+        rb = self.ray_bounds
+        if rb is None or ray_batch.dim() != 2 or ray_batch.shape[0] == 0:
+            return ray_batch
+        _lib.require_device(ray_batch, "ray_batch")
+        return rb.apply(ray_batch)
+
     def _launch_batch(self, rays, starts, chunk, coarse_model, fine_model, full):
         """render_batch as ONE library call over whole-batch buffers (nerf_amd_render_batch).  The random draws are made
         per chunk, in the reference's order (t_rand, noise0, u, noise1 of chunk 0, then of chunk 1, ...), into the rows of
@@ -536,6 +550,10 @@ class Renderer(torch.nn.Module):
         Returns the reference's dict: rgb_map, disp_map, acc_map, [raw],
         [weights, z_vals], and with N_importance > 0: rgb0, disp0, acc0, z_std.
         """
+        return self._render_rays(self._clip(ray_batch), coarse_model, fine_model, retraw, retweights, verbose, pytest)
+
+    def _render_rays(self, ray_batch, coarse_model, fine_model, retraw=False, retweights=False, verbose=False, pytest=False):
+        """render_rays behind the ray-bounds clip (render_batch, which has clipped its whole batch, calls this per chunk)."""
         _lib.require_device(ray_batch, "ray_batch")
         coarse_model, fine_model = nerf_mod.adopt(coarse_model), nerf_mod.adopt(fine_model)     # reference-class models: a twin sharing their parameters
         rays = ray_batch.detach().contiguous().float()
@@ -588,6 +606,10 @@ class Renderer(torch.nn.Module):
         of the other; results do not depend on it (random draws come from the device's one
         generator in chunk order in every mode).  Off by default: the gain is ~3 % and
         concurrent kernels blur per-kernel timings."""
+        return self._render_batch(coarse_model, fine_model, self._clip(rays_flat), chunk, retraw)
+
+    def _render_batch(self, coarse_model, fine_model, rays_flat, chunk, retraw):
+        """render_batch behind the ray-bounds clip."""
         _lib.require_device(rays_flat, "rays_flat")
         coarse_model, fine_model = nerf_mod.adopt(coarse_model), nerf_mod.adopt(fine_model)
         rays = rays_flat.detach().contiguous().float()
@@ -607,13 +629,13 @@ class Renderer(torch.nn.Module):
             return full
         if mode == "defer":            # forward-only kernels now, a backward that explains itself later (nerf._grad_request)
             with torch.no_grad():
-                plain = self.render_batch(coarse_model, fine_model, rays_flat, chunk, retraw)
+                plain = self._render_batch(coarse_model, fine_model, rays_flat, chunk, retraw)
             return nerf_mod.attach_deferred_grad(plain, deferred)
         if mode == "train":
             live = rays_flat if (torch.is_grad_enabled() and rays_flat.requires_grad) else rays
             parts = {}                     # training: autograd graph per chunk, concatenated like the reference
             for i in starts:
-                r = self.render_rays(live[i:i + chunk], coarse_model, fine_model, retraw)
+                r = self._render_rays(live[i:i + chunk], coarse_model, fine_model, retraw)
                 for k, v in r.items():
                     parts.setdefault(k, []).append(v)
             # (one chunk: the reference's torch.cat of a single tensor is a copy of it)
