@@ -631,6 +631,40 @@ int nerf_amd_occupancy_ray_grads(const int32_t *rank, const float *z, const floa
 int nerf_amd_occupancy_ray_bounds(const nerf_amd_occupancy_grid *grid, const float *rays, int32_t ray_ch, int64_t R,
                                   int32_t probes, int32_t pad, float *rays_out, float *bounds, int32_t *span, void *stream);
 
+/* Coarse depths in each ray's live stretches: the reference's stratified ladder in t in [0, 1] is kept, draw for draw, and
+ * mapped through the ray's live probes, so that equal steps of t are equal steps of LIVE length and no coarse sample is spent
+ * on the empty stretches inside (or outside) the ray's live span.  rays [R, 8|11], probes = P a power of two in 64..4096,
+ * 0 <= pad <= P, R < 2^31, t_vals [N_samples] in [0, 1] ascending (the reference's linspace), t_rand [R, N_samples] in [0, 1)
+ * required iff perturb; z_vals [R, N_samples]; live_count int32 [R], optional (NULL), receives L.  All arithmetic is fp32,
+ * every operation rounded on its own.  Per ray, with near = rays[r,6], far = rays[r,7]:
+ *   1. PROBES, exactly those of nerf_amd_occupancy_ray_bounds:  w = far - near;  probe k (0 <= k < P) sits at
+ *      t_k = near + w * ((k + 0.5) / P), the product rounded, then the sum;  its point is rays_o + rays_d t_k, the product
+ *      rounded first;  b_k = 1 when it is live by the lookup and the outside policy above (a NaN point is outside).
+ *   2. PAD:  b'_k = OR of b_j over |j - k| <= pad, 0 <= j < P.  L = the number of set b';  l_0 < ... < l_(L-1) their indices.
+ *   3. FALLBACK:  if L == 0 (a miss) or L == P (all live) the row is nerf_amd_coarse_z's for that ray, bit for bit,
+ *      its jitter in z under perturb included (one function, csrc/coarse_ladder.h, serves both kernels) -- so an
+ *      all-live grid gives what no sampler gives.
+ *   4. WARP, otherwise, for sample s:  t = t_vals[s] without perturb;  with perturb
+ *        lower = s > 0 ? 0.5 * (t_s + t_(s-1)) : t_s;   upper = s < N_samples - 1 ? 0.5 * (t_(s+1) + t_s) : t_s;
+ *        t = lower + (upper - lower) * t_rand[r, s];
+ *      then   a = min(t * (float)L, (float)L);   j = min((int)floorf(a), L - 1);   f = a - (float)j;
+ *             e = (float)l_j + f;   u = e * (1 / P) (exact);   z = near + w * u, the product rounded first.
+ *   5. lindisp != 0 is refused (NERF_AMD_EINVAL): a warp in disparity is a different definition.
+ * Bad probes, pad, grid, rays or a missing buffer are refused before any launch; R == 0 returns NERF_AMD_OK and launches
+ * nothing.  One 64-lane wave per ray; the live string is kept one 64-bit word per lane (no LDS, no atomics, no global
+ * scratch); enqueue-only (it can be captured; the grid's words are read when it runs).
+ * PROMISED (for t in [0, 1] and finite w >= 0):  rows are non-decreasing in s;  e lies in [l_j, l_j + 1]: every sample lies
+ *   in a probe interval [near + w k / P, near + w (k + 1) / P] whose padded bit is set, or exactly on that interval's
+ *   upper end;  near <= z <= near (+) (far (-) near), the rounded sum of the rounded difference.
+ * NOT PROMISED:  z <= far -- the last sample can exceed far by the rounding of near + (far - near) (seen: 4.8e-7 at far
+ *   near 6);  that a sample looks up live -- only the probe midpoints were looked up;  anything about a live stretch
+ *   shorter than one probe spacing w / P, which the probes can miss.  The depths span the gaps: compositing takes the
+ *   distance from the last sample of a stretch to the first of the next as that sample's interval, and the bins of the
+ *   hierarchical resampling can span a gap. */
+int nerf_amd_occupancy_coarse_z(const nerf_amd_occupancy_grid *grid, const float *rays, int32_t ray_ch, const float *t_vals,
+                                const float *t_rand, int64_t R, int32_t N_samples, int32_t probes, int32_t pad, int lindisp,
+                                int perturb, float *z_vals, int32_t *live_count, void *stream);
+
 /* The field at a point list: pts [n,3], viewdirs [n,3] (one per POINT; NULL for a model without view branch) -> raw [n,ch].
  * Unlike nerf_amd_nerf_forward it takes the RENDER path's choice of weight stream (tuning key 2: the folded stream of a
  * bf16 view-branch model when NERF_AMD_COPY_BF16_FOLD is current), so a compacted pass runs the kernel the dense pass

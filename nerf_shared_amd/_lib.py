@@ -45,7 +45,7 @@ EXPORTS = (
     "nerf_amd_occupancy_cull", "nerf_amd_occupancy_expand", "nerf_amd_field_points",
     "nerf_amd_render_rays_culled_workspace", "nerf_amd_render_rays_culled",
     "nerf_amd_occupancy_cull_capped", "nerf_amd_occupancy_gather_rows", "nerf_amd_occupancy_ray_grads",
-    "nerf_amd_occupancy_ray_bounds",
+    "nerf_amd_occupancy_ray_bounds", "nerf_amd_occupancy_coarse_z",
 )
 OCC_OUTSIDE_LIVE, OCC_OUTSIDE_EMPTY = 0, 1
 
@@ -167,6 +167,8 @@ def _load():
         "nerf_amd_occupancy_ray_grads": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int32, c_int32, c_void_p, c_void_p]),
         "nerf_amd_occupancy_ray_bounds": (c_int, [POINTER(OccupancyGridC), c_void_p, c_int32, c_int64, c_int32, c_int32, c_void_p, c_void_p,
                                                   c_void_p, c_void_p]),
+        "nerf_amd_occupancy_coarse_z": (c_int, [POINTER(OccupancyGridC), c_void_p, c_int32, c_void_p, c_void_p, c_int64, c_int32, c_int32,
+                                                c_int32, c_int, c_int, c_void_p, c_void_p, c_void_p]),
         "nerf_amd_field_points": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_int, c_void_p]),
         "nerf_amd_render_rays_culled_workspace": (c_int64, [POINTER(RenderCfg), c_int64, c_int32]),
         "nerf_amd_render_rays_culled": (c_int, [POINTER(RenderCfg), c_void_p, c_void_p, POINTER(RenderIO), c_int64,

@@ -1091,6 +1091,21 @@ int nerf_amd_occupancy_ray_bounds(const nerf_amd_occupancy_grid *grid, const flo
     return rc ? fail(rc, "occupancy_ray_bounds launch failed") : NERF_AMD_OK;
 }
 
+int nerf_amd_occupancy_coarse_z(const nerf_amd_occupancy_grid *grid, const float *rays, int32_t ray_ch, const float *t_vals,
+                                const float *t_rand, int64_t R, int32_t N_samples, int32_t probes, int32_t pad, int lindisp, int perturb,
+                                float *z_vals, int32_t *live_count, void *stream) {
+    OccGrid g;
+    if (int rc = occ_grid(grid, true, &g)) return rc;
+    if (lindisp) return fail(NERF_AMD_EINVAL, "occupancy_coarse_z: lindisp is not supported (a warp in disparity is a different definition)");
+    if (R < 0 || R >= ((int64_t)1 << 31) || N_samples < 1 || (ray_ch != 8 && ray_ch != 11) || probes < 64 || probes > 4096 ||
+        (probes & (probes - 1)) || pad < 0 || pad > probes || (R > 0 && (!rays || !t_vals || !z_vals || (perturb && !t_rand))))
+        return fail(NERF_AMD_EINVAL, "bad occupancy_coarse_z arguments (probes: a power of two in 64..4096; 0 <= pad <= probes; "
+                                     "t_rand is required under perturb)");
+    int rc = launch_occupancy_coarse_z(g, rays, ray_ch, t_vals, perturb ? t_rand : nullptr, R, N_samples, probes, pad, perturb ? 1 : 0,
+                                       z_vals, live_count, static_cast<hipStream_t>(stream));
+    return rc ? fail(rc, "occupancy_coarse_z launch failed") : NERF_AMD_OK;
+}
+
 int nerf_amd_field_points(const nerf_amd_model *m, const float *pts, const float *viewdirs, int64_t n, float *raw,
                           int precision, void *stream) {
     if (!m || n < 0) return fail(NERF_AMD_EINVAL, "bad field_points arguments");

@@ -256,5 +256,9 @@ int launch_occupancy_ray_grads(const int32_t *rank, const float *z, const float 
 // each ray's near / far clipped to the span over which `probes` probes of it are live; any of the three outputs may be null
 int launch_occupancy_ray_bounds(const OccGrid &g, const float *rays, int ray_ch, int64_t R, int probes, int pad, float *rays_out,
                                 float *bounds, int32_t *span, hipStream_t s);
+// coarse depths with the stratified ladder mapped through each ray's live probes (a miss and an all-live ray: the reference
+// ladder); live_count may be null, t_rand is read under perturb only
+int launch_occupancy_coarse_z(const OccGrid &g, const float *rays, int ray_ch, const float *t_vals, const float *t_rand, int64_t R, int Nc,
+                              int probes, int pad, int perturb, float *z, int32_t *live_count, hipStream_t s);
 
 }  // namespace na

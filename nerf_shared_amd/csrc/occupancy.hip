@@ -7,6 +7,7 @@
 
 #include <cstdint>
 
+#include "coarse_ladder.h"
 #include "kernels.h"
 #include "mix32.h"
 #include "pipeline.h"
@@ -458,6 +459,111 @@ int launch_occupancy_ray_bounds(const OccGrid &g, const float *rays, int ray_ch,
     if (R <= 0) return NERF_AMD_OK;
     hipLaunchKernelGGL(occupancy_ray_bounds_kernel, dim3(blocks_for(R * 64)), dim3(OC_BLOCK), 0, s, g, rays, ray_ch, R, probes, pad, rays_out,
                        bounds, span);
+    return launched();
+}
+
+// ---------------------------------------------------------------------------
+// Coarse depths in each ray's live stretches (nerf_amd.h, nerf_amd_occupancy_coarse_z): the ray-bounds probes, all P of them,
+// then the reference's stratified ladder in t mapped through the list of live probes.  One 64-lane wave per ray (four rays
+// per block).  Round q's ballot is word q of the ray's P-bit live string; lane q keeps it, so the string lies one 64-bit
+// word per lane (lanes >= P / 64 hold 0) and never leaves the registers: NO LDS (0 bytes per block), no atomics, no global
+// scratch.  Padding ORs the string with itself shifted by 1 .. pad either way, by doubling (at most 13 steps a direction),
+// a shift taking its carries from the neighbouring lanes' words.  Popcount per word, an inclusive wave prefix sum, and then
+// lane l maps samples s = l, l + 64, ...: a binary search of the prefix sums for the word that holds rank j, and of that
+// word's popcounts for its bit.  Every loop around a ballot or a shuffle is wave-uniform (the sample loop runs all 64 lanes,
+// a lane past N_samples works on the last sample and stores nothing).  A miss and an all-live ray are the shared ladder.
+// ---------------------------------------------------------------------------
+__device__ __forceinline__ uint64_t word_at(uint64_t x, int lane, int delta) {      // word lane + delta of the string, 0 past either end
+    const int src = lane + delta;
+    const uint64_t v = __shfl(x, src & 63, 64);
+    return (src >= 0 && src < 64) ? v : 0;
+}
+
+template <bool UP>
+__device__ __forceinline__ uint64_t shift_string(uint64_t x, int lane, int s) {     // the string moved s bits (1 <= s <= 4096) up / down
+    const int ws = s >> 6, bs = s & 63;
+    const uint64_t a = word_at(x, lane, UP ? -ws : ws), b = word_at(x, lane, UP ? -ws - 1 : ws + 1);
+    if (bs == 0) return a;
+    return UP ? (a << bs) | (b >> (64 - bs)) : (a >> bs) | (b << (64 - bs));
+}
+
+__global__ __launch_bounds__(OC_BLOCK) void occupancy_coarse_z_kernel(OccGrid g, const float *rays, int ray_ch, const float *t_vals,
+                                                                      const float *t_rand, int64_t R, int Nc, int P, int pad, int perturb,
+                                                                      float *z, int32_t *live_count) {
+    const int lane = threadIdx.x & 63;
+    const int rounds = P >> 6;
+    const float inv_p = 1.0f / (float)P;                              // exact
+    const int64_t ray = (int64_t)blockIdx.x * (OC_BLOCK / 64) + (threadIdx.x >> 6);
+    if (ray >= R) return;                                             // (whole waves leave: the ballots and shuffles below see all 64 lanes)
+    const float *r = rays + ray * ray_ch;
+    const float o[3] = {r[0], r[1], r[2]}, d[3] = {r[3], r[4], r[5]};
+    const float near = r[6], far = r[7];
+    const float w = far - near;
+    uint64_t bits = 0;
+    for (int q = 0; q < rounds; ++q) {
+        const uint64_t m = probe_round(g, o, d, near, w, q * 64 + lane, inv_p);
+        if (lane == q) bits = m;
+    }
+    if (pad > 0) {
+        uint64_t up = bits, down = bits;                              // the OR over shifts 0 .. covered, each way
+        for (int covered = 0; covered < pad;) {
+            const int step = min(covered + 1, pad - covered);
+            up |= shift_string<true>(up, lane, step);
+            down |= shift_string<false>(down, lane, step);
+            covered += step;
+        }
+        bits = lane < rounds ? (up | down) : 0;                       // (what was pushed past probe P - 1 is dropped)
+    }
+    int incl = __popcll(bits);
+#pragma unroll
+    for (int m = 1; m < 64; m <<= 1) {
+        const int below = __shfl_up(incl, m, 64);
+        if (lane >= m) incl += below;
+    }
+    const int L = __shfl(incl, 63, 64);
+    if (live_count && lane == 0) live_count[ray] = L;
+    float *zr = z + ray * Nc;
+    const float *rand = perturb ? t_rand + ray * Nc : nullptr;
+    if (L == 0 || L == P) {                                           // a miss, or nothing to drop: the reference ladder
+        for (int s = lane; s < Nc; s += 64) zr[s] = ladder_z(near, far, t_vals, s, Nc, 0, perturb, perturb ? rand[s] : 0.0f);
+        return;
+    }
+    const float fl = (float)L;
+    for (int s0 = 0; s0 < Nc; s0 += 64) {
+        const int s = min(s0 + lane, Nc - 1);
+        float t = t_vals[s];
+        if (perturb) {
+            float upper = t, lower = t;
+            if (s > 0) lower = 0.5f * (t + t_vals[s - 1]);
+            if (s < Nc - 1) upper = 0.5f * (t_vals[s + 1] + t);
+            t = lower + (upper - lower) * rand[s];
+        }
+        const float a = fminf(t * fl, fl);
+        const int j = min((int)floorf(a), L - 1);
+        const float f = a - (float)j;
+        int k = 0;                                                    // the word that holds rank j: the number of words with incl <= j
+#pragma unroll
+        for (int step = 32; step >= 1; step >>= 1)
+            if (__shfl(incl, k + step - 1, 64) <= j) k += step;
+        const uint64_t m = __shfl(bits, k, 64);
+        int rank = j - (__shfl(incl, k, 64) - __popcll(m));           // ... and the rank of the bit inside it
+        int pos = 0;
+#pragma unroll
+        for (int width = 32; width >= 1; width >>= 1) {
+            const int c = __popcll((m >> pos) & (((uint64_t)1 << width) - 1));
+            if (rank >= c) { rank -= c; pos += width; }
+        }
+        const float e = (float)(k * 64 + pos) + f;
+        const float u = e * inv_p;                                    // exact
+        if (s0 + lane < Nc) zr[s0 + lane] = mul_then_add(w, u, near);
+    }
+}
+
+int launch_occupancy_coarse_z(const OccGrid &g, const float *rays, int ray_ch, const float *t_vals, const float *t_rand, int64_t R, int Nc,
+                              int probes, int pad, int perturb, float *z, int32_t *live_count, hipStream_t s) {
+    if (R <= 0) return NERF_AMD_OK;
+    hipLaunchKernelGGL(occupancy_coarse_z_kernel, dim3(blocks_for(R * 64)), dim3(OC_BLOCK), 0, s, g, rays, ray_ch, t_vals, t_rand, R, Nc,
+                       probes, pad, perturb, z, live_count);
     return launched();
 }
 

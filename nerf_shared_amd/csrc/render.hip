@@ -11,6 +11,7 @@
 #include <cstring>
 #include <math.h>
 
+#include "coarse_ladder.h"
 #include "kernels.h"
 #include "launch_util.h"
 
@@ -71,11 +72,7 @@ __device__ __forceinline__ T wave_sum(T v) {
 // ---------------------------------------------------------------------------
 // z_vals of the coarse pass: render_utils.py:105-129
 // ---------------------------------------------------------------------------
-__device__ __forceinline__ float z_of_t(float near, float far, float t, int lindisp) {
-    if (!lindisp) return near * (1.0f - t) + far * t;
-    return 1.0f / (1.0f / near * (1.0f - t) + 1.0f / far * t);
-}
-
+// (z_of_t and the jitter: coarse_ladder.h, shared with the fallback rows of occupancy_coarse_z_kernel)
 __global__ __launch_bounds__(256) void coarse_z_kernel(const float *rays, int ray_stride, const float *t_vals,
                                                        const float *t_rand, int64_t R, int Nc, int lindisp,
                                                        int perturb, float *z) {
@@ -84,14 +81,7 @@ __global__ __launch_bounds__(256) void coarse_z_kernel(const float *rays, int ra
         const int64_t r = i / Nc;
         const int s = (int)(i - r * Nc);
         const float near = rays[r * ray_stride + 6], far = rays[r * ray_stride + 7];
-        float zc = z_of_t(near, far, t_vals[s], lindisp);
-        if (perturb) {
-            float upper = zc, lower = zc;
-            if (s + 1 < Nc) upper = 0.5f * (z_of_t(near, far, t_vals[s + 1], lindisp) + zc);
-            if (s > 0) lower = 0.5f * (zc + z_of_t(near, far, t_vals[s - 1], lindisp));
-            zc = lower + (upper - lower) * t_rand[i];
-        }
-        z[i] = zc;
+        z[i] = ladder_z(near, far, t_vals, s, Nc, lindisp, perturb, perturb ? t_rand[i] : 0.0f);
     }
 }
 

@@ -239,8 +239,13 @@ class Renderer(torch.nn.Module):
         tensors of ``outs`` (rows [0, R))."""
         dev = rays.device
         hc, hf, cfg, out_ch = self._handles(dev, coarse_model, fine_model)
-        io, keep = self._chunk_io(rays, cfg, out_ch, outs, pytest)
+        z_pre = None
+        if self.coarse_sampler is not None and rays.shape[0] > 0:
+            z_pre = torch.empty(rays.shape[0], int(self.N_samples), device=dev, dtype=torch.float32)
+        io, keep = self._chunk_io(rays, cfg, out_ch, outs, pytest, z_pre=z_pre)
         with torch.cuda.device(dev):
+            if z_pre is not None:
+                self._coarse_z(rays, keep[1], z_pre)                   # (keep[1]: the t_rand that _chunk_io drew)
             _lib.check(lib.nerf_amd_render_rays(cfg, hc, hf, io, rays.shape[0], _lib.stream_of(dev)), "nerf_amd_render_rays")
         # keep the draws alive until the stream has consumed them (caching allocator is stream-ordered)
         return keep
@@ -271,6 +276,11 @@ class Renderer(torch.nn.Module):
         hc, hf, cfg, out_ch = self._handles(dev, coarse_model, fine_model)
         R, Nc, Ni = rays.shape[0], int(self.N_samples), int(self.N_importance)
         t_rand, _, _, u, t_lin = self._draws(R, dev, pytest)
+        z_pre = None
+        if self.coarse_sampler is not None and R > 0:
+            z_pre = torch.empty(R, Nc, device=dev, dtype=torch.float32)
+            with torch.cuda.device(dev):
+                self._coarse_z(rays, t_rand, z_pre)
         g = grid._c()
         counts = (ctypes.c_int64 * 4)()
         step = self.CULL_GROUP_RAYS
@@ -283,6 +293,7 @@ class Renderer(torch.nn.Module):
             io.t_rand = None if t_rand is None else t_rand[i:i + step].data_ptr()
             io.u = None if u is None else u[i:i + step].data_ptr()
             io.t_lin_imp = _lib.ptr(t_lin)
+            io.z_coarse = None if z_pre is None else z_pre[i:i + step].data_ptr()
             for k in ('rgb_map', 'disp_map', 'acc_map', 'rgb0', 'disp0', 'acc0', 'z_std', 'raw', 'weights', 'z_vals'):
                 v = outs.get(k)
                 setattr(io, k, None if v is None else v[i:i + step].data_ptr())
@@ -292,7 +303,7 @@ class Renderer(torch.nn.Module):
                            "nerf_amd_render_rays_culled")
             for j, k in enumerate(('coarse_live', 'coarse_total', 'fine_live', 'fine_total')):
                 stats[k] += int(counts[j])
-        return (rays, t_rand, u, ws)
+        return (rays, t_rand, u, z_pre, ws)
 
     @staticmethod
     def _new_cull_stats():
@@ -341,6 +352,36 @@ class Renderer(torch.nn.Module):
             return ray_batch
         _lib.require_device(ray_batch, "ray_batch")
         return rb.apply(ray_batch)
+
+    # ------------------------------------------------------------------ coarse sampler (opt-in)
+    coarse_sampler = None         # a nerf_shared_amd.occupancy.LiveSampler: every render path takes its coarse depths from it --
+                                  # the same stratified ladder and draws, mapped through each ray's live probes -- instead of
+                                  # nerf_amd_coarse_z.  None: the reference ladder, launch for launch.
+
+    def _check_sampler(self, dev):
+        """What a set coarse_sampler cannot do is refused before any draw or launch."""
+        cs = self.coarse_sampler
+        if cs is None:
+            return
+        if self.lindisp:
+            raise _lib.NerfAmdError("Renderer.coarse_sampler is set and lindisp is on: the live-stretch warp is defined in depth, not "
+                                    "in disparity.  Set lindisp = False or renderer.coarse_sampler = None")
+        if cs.grid.device != dev:
+            raise _lib.NerfAmdError("Renderer.coarse_sampler is on %s, the rays on %s" % (cs.grid.device, dev))
+
+    def _coarse_z(self, rays, t_rand, z_out):
+        """The coarse depths of contiguous fp32 rays [R, 8|11] into z_out [R, N_samples], on the current stream: nerf_amd_coarse_z,
+        or the coarse_sampler's kernel when one is set.  t_rand [R, N_samples] | None: the jitter draws (read under perturb).
+        Called with the rays' device current (inside torch.cuda.device(dev)), like the library calls around it."""
+        dev, Nc = rays.device, int(self.N_samples)
+        cs = self.coarse_sampler
+        if cs is not None:
+            self._check_sampler(dev)
+            cs.fill(rays, _linspace01(Nc, dev), t_rand if self.perturb > 0. else None, z_out)
+            return
+        _lib.check(lib.nerf_amd_coarse_z(rays.data_ptr(), rays.shape[1], _linspace01(Nc, dev).data_ptr(), _lib.ptr(t_rand),
+                                         rays.shape[0], Nc, int(bool(self.lindisp)), int(self.perturb > 0.), z_out.data_ptr(),
+                                         _lib.stream_of(dev)), "nerf_amd_coarse_z")
 
     def _launch_batch(self, rays, starts, chunk, coarse_model, fine_model, full):
         """render_batch as ONE library call over whole-batch buffers (nerf_amd_render_batch).  The random draws are made
@@ -396,9 +437,7 @@ class Renderer(torch.nn.Module):
         ws = _workspace(dev, lib.nerf_amd_render_batch_workspace(cfg, N, out_ch))
         io.workspace, io.workspace_bytes = ws.data_ptr(), ws.numel()
         with torch.cuda.device(dev):
-            _lib.check(lib.nerf_amd_coarse_z(rays.data_ptr(), rays.shape[1], _linspace01(Nc, dev).data_ptr(),
-                                             _lib.ptr(t_all), N, Nc, int(bool(self.lindisp)), int(self.perturb > 0.),
-                                             z_all.data_ptr(), _lib.stream_of(dev)), "nerf_amd_coarse_z")
+            self._coarse_z(rays, t_all, z_all)
             _lib.check(lib.nerf_amd_render_batch(cfg, hc, hf, io, N, _lib.stream_of(dev)), "nerf_amd_render_batch")
         # the library's side stream reads these too; its work is ordered before the caller's stream continues, so
         # releasing them to the caching allocator (stream-ordered on the caller's stream) is safe
@@ -426,9 +465,7 @@ class Renderer(torch.nn.Module):
             counts[j] = r.shape[0]
             keep.append(alive)
         with torch.cuda.device(dev):
-            _lib.check(lib.nerf_amd_coarse_z(rays.data_ptr(), rays.shape[1], _linspace01(Nc, dev).data_ptr(),
-                                             _lib.ptr(t_all), N, Nc, int(bool(self.lindisp)), int(self.perturb > 0.),
-                                             z_all.data_ptr(), _lib.stream_of(dev)), "nerf_amd_coarse_z")
+            self._coarse_z(rays, t_all, z_all)
             _lib.check(lib.nerf_amd_render_chunks(cfg, hc, hf, ios, counts, n, _lib.stream_of(dev)), "nerf_amd_render_chunks")
         return keep
 
@@ -467,9 +504,7 @@ class Renderer(torch.nn.Module):
         stream = _lib.stream_of(dev)
         z = torch.empty(R, Nc, **f)
         with torch.cuda.device(dev):
-            _lib.check(lib.nerf_amd_coarse_z(rays.data_ptr(), rays.shape[1], _linspace01(Nc, dev).data_ptr(), _lib.ptr(t_rand),
-                                             R, Nc, int(bool(self.lindisp)), int(self.perturb > 0.), z.data_ptr(), stream),
-                       "nerf_amd_coarse_z")
+            self._coarse_z(rays, t_rand, z)
         rays_d = rays[:, 3:6]            # a view: composite gradients with respect to |d| flow back into `rays`
 
         cull = self.train_occupancy
@@ -562,6 +597,7 @@ class Renderer(torch.nn.Module):
         self._check_model(coarse_model, "coarse_model")
         if fine_model is not None:
             self._check_model(fine_model, "fine_model")
+        self._check_sampler(rays.device)
         mode, deferred = self._grad_mode(coarse_model, fine_model, ray_batch) if rays.shape[0] > 0 else ("none", None)
         if self.occupancy is not None:
             self._check_cullable(mode)
@@ -615,6 +651,7 @@ class Renderer(torch.nn.Module):
         rays = rays_flat.detach().contiguous().float()
         self._check_model(coarse_model, "coarse_model")
         N, dev = rays.shape[0], rays.device
+        self._check_sampler(dev)
         out_ch = 4 if coarse_model.use_viewdirs else coarse_model.output_ch
         starts = list(range(0, N, chunk))
         mode, deferred = self._grad_mode(coarse_model, fine_model, rays_flat) if N > 0 else ("none", None)

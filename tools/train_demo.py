@@ -9,6 +9,8 @@ mse(rgb) + mse(rgb0) -> Adam with exponential lr decay).  Prints PSNR on a held-
 --occupancy RES trains with an occupancy grid of RES^3 cells (occupancy.TrainCull, Renderer.train_occupancy; see train_culled).
 --ray-bounds P also clips every ray's near / far to the grid's live span along it, probed at P points (occupancy.RayBounds,
 Renderer.ray_bounds), from the moment the grid is filled, and for the test renders.
+--live-sampler P places the coarse samples in each ray's live stretches, probed at P points (occupancy.LiveSampler,
+Renderer.coarse_sampler; --live-sampler-pad widens every stretch), from the same moment and for the test renders.  Off by default.
 """
 import argparse
 import json
@@ -70,7 +72,7 @@ def write_blender_scene(root, H, W, poses, images, i_train, i_test):
 
 def train_culled(renderer, coarse, fine, opt, H, W, K, chunk, n_rand, next_batch, lr_at, first, steps, box, resolution,
                  warmup=200, refresh=16, calibration_steps=8, slabs=8, margin=1.25, outside="empty", verbose=True,
-                 ray_bounds_probes=None, ray_bounds_pad=32):
+                 ray_bounds_probes=None, ray_bounds_pad=32, live_sampler_probes=None, live_sampler_pad=1):
     """The training loop with an occupancy grid, steps [first, first + steps):
       1. `warmup` steps through a captured DENSE step (utils.CapturedTrainStep): the field has to mean something first;
       2. OccupancyGrid(box, resolution).fill_from_density([coarse, fine]);
@@ -87,6 +89,8 @@ def train_culled(renderer, coarse, fine, opt, H, W, K, chunk, n_rand, next_batch
     rendering a trained model at pad 1 loses nothing.  The cause was not isolated.  We SUPPOSE the compositing's 1e10-long
     last interval (the last sample of a ray should lie in space the model has learnt to be empty) and a grid that follows a
     model which is only ever sampled inside the grid's own span.
+    live_sampler_probes = P: from step 2 on renderer.coarse_sampler = LiveSampler(grid, P, live_sampler_pad) as well (it stays
+    set when this returns, like the bounds).  Off unless asked for; what training with it was measured to do: DESIGN.md 8e.3.
     next_batch(i) -> (rays [2, n_rand, 3], target [n_rand, 3]); lr_at(i): the learning rate AFTER step i (main.py:108-112).
     Returns (last loss, the TrainCull or None when the run ended inside the warm-up, its stats())."""
     def set_lr(i):
@@ -114,6 +118,9 @@ def train_culled(renderer, coarse, fine, opt, H, W, K, chunk, n_rand, next_batch
     if ray_bounds_probes:
         occupancy._probes_pad(ray_bounds_probes, ray_bounds_pad)       # a bad pair is refused now, not after the warm-up
         renderer.ray_bounds = None
+    if live_sampler_probes:
+        occupancy._probes_pad(live_sampler_probes, live_sampler_pad)
+        renderer.coarse_sampler = None
     if min(warmup, steps) > 0:
         dense = utils.CapturedTrainStep(renderer, H, W, K, chunk, coarse, fine, opt, n_rand)
         while i < min(first + warmup, last):
@@ -128,6 +135,8 @@ def train_culled(renderer, coarse, fine, opt, H, W, K, chunk, n_rand, next_batch
     renderer.train_occupancy = cull
     if ray_bounds_probes:
         renderer.ray_bounds = occupancy.RayBounds(grid, ray_bounds_probes, ray_bounds_pad)
+    if live_sampler_probes:
+        renderer.coarse_sampler = occupancy.LiveSampler(grid, live_sampler_probes, live_sampler_pad)
     for _ in range(min(calibration_steps, last - i)):
         loss = eager_step(i)
         set_lr(i)
@@ -183,10 +192,12 @@ def train_culled(renderer, coarse, fine, opt, H, W, K, chunk, n_rand, next_batch
 
 
 def run(steps=600, res=64, views=12, n_rand=1024, seed=0, verbose=True, scene_dir=None, multires=10, multires_views=4,
-        lrate=5e-4, ss=1, occupancy_res=None, occupancy_warmup=200, occupancy_refresh=16, ray_bounds_probes=None, ray_bounds_pad=32):
+        lrate=5e-4, ss=1, occupancy_res=None, occupancy_warmup=200, occupancy_refresh=16, ray_bounds_probes=None, ray_bounds_pad=32,
+        live_sampler_probes=None, live_sampler_pad=1):
     """scene_dir: write the scene to disk in the Blender format first and train from what
     utils.load_datasets reads back (8-bit frames) instead of from the in-memory float images.
-    ray_bounds_probes, ray_bounds_pad (with occupancy_res): train_culled's; the test render after training is clipped by the same grid."""
+    ray_bounds_probes, ray_bounds_pad (with occupancy_res): train_culled's; the test render after training is clipped by the same grid.
+    live_sampler_probes, live_sampler_pad (with occupancy_res): train_culled's; the test render uses the same sampler."""
     torch.manual_seed(seed)
     np.random.seed(seed)
     dev = torch.device("cuda:0")
@@ -235,7 +246,8 @@ def run(steps=600, res=64, views=12, n_rand=1024, seed=0, verbose=True, scene_di
         loss, _, cull_stats = train_culled(renderer, coarse, fine, opt, H, W, K, 32768, N_rand, next_batch,
                                            lambda i: args.lrate * (0.1 ** (i / (args.lrate_decay * 1000))), 0, steps, SPHERE_BOX,
                                            int(occupancy_res), occupancy_warmup, occupancy_refresh, verbose=verbose,
-                                           ray_bounds_probes=ray_bounds_probes, ray_bounds_pad=ray_bounds_pad)
+                                           ray_bounds_probes=ray_bounds_probes, ray_bounds_pad=ray_bounds_pad,
+                                           live_sampler_probes=live_sampler_probes, live_sampler_pad=live_sampler_pad)
         renderer.train_occupancy = None
     for i in range(0 if occupancy_res else steps):          # the dense loop, eager (main.py:77-112)
         batch_rays, target, rays_rgb, i_batch = utils.sample_random_ray_batch(args, images, poses_t, rays_rgb, N_rand, use_batching,
@@ -259,6 +271,9 @@ def run(steps=600, res=64, views=12, n_rand=1024, seed=0, verbose=True, scene_di
         if ray_bounds_probes:
             out["occupancy"]["ray_bounds_probes"] = int(ray_bounds_probes)
             out["occupancy"]["ray_bounds_pad"] = int(ray_bounds_pad)
+        if live_sampler_probes:
+            out["occupancy"]["live_sampler_probes"] = int(live_sampler_probes)
+            out["occupancy"]["live_sampler_pad"] = int(live_sampler_pad)
     return out, (coarse, fine, opt, args, renderer, (H, W, K), poses_t, images, i_test)
 
 
@@ -281,8 +296,12 @@ if __name__ == "__main__":
     ap.add_argument("--ray-bounds", type=int, default=0, metavar="P", help="with --occupancy: clip each ray's near / far to the grid's "
                     "live span, probed at P points (a power of two in 64..4096; 0: off)")
     ap.add_argument("--ray-bounds-pad", type=int, default=32, metavar="N", help="probe spacings the span is widened by while training")
+    ap.add_argument("--live-sampler", type=int, default=0, metavar="P", help="with --occupancy: place the coarse samples in each ray's "
+                    "live stretches, probed at P points (a power of two in 64..4096; 0: off)")
+    ap.add_argument("--live-sampler-pad", type=int, default=1, metavar="N", help="probes every live stretch is widened by, either way")
     a = ap.parse_args()
     print(json.dumps(run(a.steps, a.res, a.views, n_rand=a.n_rand, seed=a.seed, scene_dir=a.scene_dir, multires=a.multires,
                          multires_views=a.multires_views, lrate=a.lrate, ss=a.ss, verbose=not a.quiet, occupancy_res=a.occupancy or None,
                          occupancy_warmup=a.occupancy_warmup, occupancy_refresh=a.occupancy_refresh,
-                         ray_bounds_probes=a.ray_bounds or None, ray_bounds_pad=a.ray_bounds_pad)[0]))
+                         ray_bounds_probes=a.ray_bounds or None, ray_bounds_pad=a.ray_bounds_pad,
+                         live_sampler_probes=a.live_sampler or None, live_sampler_pad=a.live_sampler_pad)[0]))
