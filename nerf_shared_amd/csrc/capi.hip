@@ -711,20 +711,6 @@ int nerf_amd_resample(const float *z_coarse, const float *weights, const float *
     return rc ? fail(rc, "resample launch failed") : NERF_AMD_OK;
 }
 
-int64_t nerf_amd_render_rays_workspace(const nerf_amd_render_cfg *cfg, int64_t R, int32_t out_ch) {
-    if (!cfg || R < 0) return -1;
-    const size_t Nc = cfg->N_samples, Nf = cfg->N_samples + cfg->N_importance;
-    size_t b = 0;
-    b += align_up(R * Nc * sizeof(float));                 // z coarse
-    b += align_up(R * Nc * out_ch * sizeof(float));        // raw coarse
-    b += align_up(R * Nc * sizeof(float));                 // weights coarse
-    if (cfg->N_importance > 0) {
-        b += align_up(R * Nf * sizeof(float));             // z fine
-        b += align_up(R * Nf * out_ch * sizeof(float));    // raw fine
-    }
-    return (int64_t)b;
-}
-
 }  // extern "C"
 
 // ---- render_rays over one chunk's buffers, in stages: z_vals, coarse field, coarse compositing (+ resampling),
@@ -739,6 +725,18 @@ struct ChunkPlan {
     bool has_vd;
     float *z_c, *raw_c, *w_c, *z_f, *raw_f;
 };
+
+// The workspace of one render_rays call, stated once: z / raw / weights of the coarse pass, then with a fine pass its z / raw.
+// Counts the bytes (nerf_amd_render_rays_workspace); with `p` and `base` it also carves them (plan_chunk).
+size_t rays_ws_bytes(int64_t R, size_t Nc, size_t Ni, size_t och, ChunkPlan *p, char *base) {
+    size_t b = 0;
+    auto take = [&](size_t bytes) { float *q = base ? reinterpret_cast<float *>(base + b) : nullptr; b += align_up(bytes); return q; };
+    const size_t Nf = Nc + Ni;
+    float *z_c = take(R * Nc * sizeof(float)), *raw_c = take(R * Nc * och * sizeof(float)), *w_c = take(R * Nc * sizeof(float));
+    float *z_f = Ni ? take(R * Nf * sizeof(float)) : nullptr, *raw_f = Ni ? take(R * Nf * och * sizeof(float)) : nullptr;
+    if (p) { p->z_c = z_c; p->raw_c = raw_c; p->w_c = w_c; p->z_f = z_f; p->raw_f = raw_f; }
+    return b;
+}
 
 int plan_chunk(const nerf_amd_render_cfg *cfg, const nerf_amd_model *coarse, const nerf_amd_model *fine,
                const nerf_amd_render_io *io, int64_t R, ChunkPlan *p) {
@@ -762,20 +760,12 @@ int plan_chunk(const nerf_amd_render_cfg *cfg, const nerf_amd_model *coarse, con
     const bool has_vd = io->ray_ch > 8;
     if ((coarse->prog.arch.use_viewdirs != 0) != has_vd || (fm->prog.arch.use_viewdirs != 0) != has_vd)
         return fail(NERF_AMD_EINVAL, "ray batch width does not match the models' use_viewdirs");
-    if (io->workspace_bytes < nerf_amd_render_rays_workspace(cfg, R, och) || !io->workspace)
+    if (io->workspace_bytes < (int64_t)rays_ws_bytes(R, Nc, Ni, och, nullptr, nullptr) || !io->workspace)
         return fail(NERF_AMD_EINVAL, "workspace too small");
     p->cfg = cfg; p->coarse = coarse; p->fm = fm; p->io = io; p->R = R;
     p->Nc = Nc; p->Ni = Ni; p->Nf = Nf; p->och = och; p->has_vd = has_vd;
-
-    char *w = static_cast<char *>(io->workspace);
-    auto take = [&](size_t bytes) { float *q = reinterpret_cast<float *>(w); w += align_up(bytes); return q; };
-    p->z_c = take(R * Nc * sizeof(float));
-    p->raw_c = take(R * Nc * och * sizeof(float));
-    p->w_c = take(R * Nc * sizeof(float));
-    p->z_f = p->raw_f = nullptr;
-    if (Ni > 0) {
-        p->z_f = take(R * (size_t)Nf * sizeof(float));
-        p->raw_f = take(R * (size_t)Nf * och * sizeof(float));
+    rays_ws_bytes(R, Nc, Ni, och, p, static_cast<char *>(io->workspace));
+    if (Ni > 0) {      // what the caller wants back is written in place
         if (io->z_vals) p->z_f = io->z_vals;
         if (io->raw) p->raw_f = io->raw;
     } else {
@@ -802,16 +792,14 @@ int stage_z(ChunkPlan &p, hipStream_t s) {
     return rc ? fail(rc, "coarse_z launch failed") : NERF_AMD_OK;
 }
 
+// the no-grad render path's choice of weight stream (stage_field, field_points): the folded one unless tuning forbids it
+int fold_wanted() { return g_fold.load(std::memory_order_relaxed) != 1 ? FOLD_IF_CURRENT : FOLD_NEVER; }
+
 int stage_field(const ChunkPlan &p, bool fine_pass, hipStream_t s) {
-    const int fold_wanted = g_fold.load(std::memory_order_relaxed) != 1 ? FOLD_IF_CURRENT : FOLD_NEVER;      // the no-grad render path
     MlpArgs a{};
     set_inputs(a, nullptr, nullptr, p.io->rays, p.io->ray_ch, fine_pass ? p.z_f : p.z_c, p.has_vd);
-    if (!fine_pass) {
-        a.P = p.R * p.Nc; a.S = p.Nc; a.out = p.raw_c;
-        return run_field(p.coarse, a, p.cfg->precision, s, fold_wanted);
-    }
-    a.P = p.R * (int64_t)p.Nf; a.S = p.Nf; a.out = p.raw_f;
-    return run_field(p.fm, a, p.cfg->precision, s, fold_wanted);
+    a.S = fine_pass ? p.Nf : p.Nc; a.P = p.R * (int64_t)a.S; a.out = fine_pass ? p.raw_f : p.raw_c;
+    return run_field(fine_pass ? p.fm : p.coarse, a, p.cfg->precision, s, fold_wanted());
 }
 
 CompositeJob final_job(const ChunkPlan &p) {       // compositing of the last pass of a chunk
@@ -852,21 +840,39 @@ int stage_mid(const ChunkPlan &p, const ChunkPlan *prev, hipStream_t s) {
         return fail(rc, lds_msg("render_rays (compositing + resampling)", resample_lds_bytes(p.Nc, p.Ni, true)));
     return rc ? fail(rc, "composite/resample launch failed") : NERF_AMD_OK;
 }
+
+// The stage order, walked once for every entry that runs its chunks one after the other on one stream: per chunk z, coarse
+// field, then either the final compositing (no fine pass) or mid and fine field -- with the final compositing of chunk k-1
+// folded into chunk k's mid launch, and the last chunk's as a launch of its own.  `field(plan, fine_pass, s)` is the field
+// stage: stage_field, or the culled one.  One plan: mid, fine field and final are three launches.
+template <class FieldStage>
+int walk_chunks(ChunkPlan *plans, int n, FieldStage field, hipStream_t s) {
+    int rc = 0;
+    for (int k = 0; k < n && !rc; ++k) {
+        ChunkPlan &p = plans[k];
+        if ((rc = stage_z(p, s)) || (rc = field(p, false, s))) break;
+        if (p.Ni == 0) { rc = stage_final(p, s); continue; }
+        if ((rc = stage_mid(p, k > 0 ? &plans[k - 1] : nullptr, s))) break;
+        rc = field(p, true, s);
+    }
+    if (!rc && n > 0 && plans[n - 1].Ni > 0) rc = stage_final(plans[n - 1], s);
+    return rc;
+}
 }  // namespace
 
 extern "C" {
+
+int64_t nerf_amd_render_rays_workspace(const nerf_amd_render_cfg *cfg, int64_t R, int32_t out_ch) {
+    if (!cfg || R < 0) return -1;
+    return (int64_t)rays_ws_bytes(R, cfg->N_samples, cfg->N_importance > 0 ? cfg->N_importance : 0, out_ch, nullptr, nullptr);
+}
 
 int nerf_amd_render_rays(const nerf_amd_render_cfg *cfg, const nerf_amd_model *coarse, const nerf_amd_model *fine,
                          const nerf_amd_render_io *io, int64_t R, void *stream) {
     if (R == 0 && cfg && coarse && io) return NERF_AMD_OK;
     ChunkPlan p;
-    int rc = plan_chunk(cfg, coarse, fine, io, R, &p);
-    if (rc) return rc;
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    if ((rc = stage_z(p, s)) || (rc = stage_field(p, false, s))) return rc;
-    if (p.Ni == 0) return stage_final(p, s);
-    if ((rc = stage_mid(p, nullptr, s)) || (rc = stage_field(p, true, s))) return rc;
-    return stage_final(p, s);
+    if (int rc = plan_chunk(cfg, coarse, fine, io, R, &p)) return rc;
+    return walk_chunks(&p, 1, stage_field, static_cast<hipStream_t>(stream));
 }
 
 int nerf_amd_render_chunks(const nerf_amd_render_cfg *cfg, const nerf_amd_model *coarse, const nerf_amd_model *fine,
@@ -887,17 +893,7 @@ int nerf_amd_render_chunks(const nerf_amd_render_cfg *cfg, const nerf_amd_model 
     for (int i = 0; i + 1 < n; ++i)
         if (plans[i].io->workspace == plans[i + 1].io->workspace)
             return fail(NERF_AMD_EINVAL, "consecutive chunks must use distinct workspaces");
-    int rc = 0;
-    for (int k = 0; k < n && !rc; ++k) {
-        ChunkPlan &p = plans[k];
-        if ((rc = stage_z(p, s)) || (rc = stage_field(p, false, s))) break;
-        if (p.Ni == 0) { rc = stage_final(p, s); continue; }
-        // one launch: this chunk's coarse compositing + resampling, and the previous chunk's final compositing
-        if ((rc = stage_mid(p, k > 0 ? &plans[k - 1] : nullptr, s))) break;
-        rc = stage_field(p, true, s);
-    }
-    if (!rc && n > 0 && plans[n - 1].Ni > 0) rc = stage_final(plans[n - 1], s);
-    return rc;
+    return walk_chunks(plans.data(), n, stage_field, s);
 }
 
 }  // extern "C"
@@ -933,11 +929,10 @@ int64_t occ_cells(const int32_t n[3]) { return (int64_t)n[0] * n[1] * n[2]; }
 // the field at a point list, with the render path's choice of weight stream (stage_field)
 int field_points(const nerf_amd_model *m, const float *pts, const float *viewdirs, int64_t n, float *raw, int precision, hipStream_t s) {
     if (n == 0) return NERF_AMD_OK;
-    const int fold_wanted = g_fold.load(std::memory_order_relaxed) != 1 ? FOLD_IF_CURRENT : FOLD_NEVER;
     MlpArgs a{};
     set_inputs(a, pts, viewdirs, nullptr, 0, nullptr, true);      // (run_field drops viewdirs for a model without view branch)
     a.P = n; a.S = 1; a.out = raw;
-    return run_field(m, a, precision, s, fold_wanted);
+    return run_field(m, a, precision, s, fold_wanted());
 }
 
 // scratch of the culled passes behind the dense workspace: one pass's worth, reused by the second
@@ -1129,8 +1124,7 @@ int nerf_amd_render_rays_culled(const nerf_amd_render_cfg *cfg, const nerf_amd_m
     if (cfg && cfg->use_noise) return fail(NERF_AMD_EINVAL, "render_rays_culled: sigma noise would resurrect culled samples (use_noise must be 0)");
     if (R == 0 && cfg && coarse && io) return NERF_AMD_OK;
     ChunkPlan p;
-    int rc = plan_chunk(cfg, coarse, fine, io, R, &p);
-    if (rc) return rc;
+    if (int rc = plan_chunk(cfg, coarse, fine, io, R, &p)) return rc;
     if (R * (int64_t)p.Nf >= ((int64_t)1 << 31)) return fail(NERF_AMD_EINVAL, "render_rays_culled: R * samples must stay below 2^31");
     if (io->workspace_bytes < nerf_amd_render_rays_culled_workspace(cfg, R, p.och)) return fail(NERF_AMD_EINVAL, "workspace too small");
     hipStream_t s = static_cast<hipStream_t>(stream);
@@ -1139,13 +1133,13 @@ int nerf_amd_render_rays_culled(const nerf_amd_render_cfg *cfg, const nerf_amd_m
         return fail(NERF_AMD_EINVAL, "render_rays_culled synchronises the stream: it cannot be captured in a graph");
     CullWs w;
     cull_ws_bytes(R * (int64_t)p.Nf, p.och, &w, static_cast<char *>(io->workspace) + nerf_amd_render_rays_workspace(cfg, R, p.och));
-    int64_t live = 0;
-    if ((rc = stage_z(p, s)) || (rc = stage_field_culled(p, false, g, w, &live, s))) return rc;
-    if (stats) { stats[0] = live; stats[1] = R * (int64_t)p.Nc; }
-    if (p.Ni == 0) return stage_final(p, s);
-    if ((rc = stage_mid(p, nullptr, s)) || (rc = stage_field_culled(p, true, g, w, &live, s))) return rc;
-    if (stats) { stats[2] = live; stats[3] = R * (int64_t)p.Nf; }
-    return stage_final(p, s);
+    auto field = [&](const ChunkPlan &q, bool fine_pass, hipStream_t fs) {      // the culled field stage; fills its pass's two counts
+        int64_t live = 0;
+        const int frc = stage_field_culled(q, fine_pass, g, w, &live, fs);
+        if (!frc && stats) { stats[fine_pass ? 2 : 0] = live; stats[fine_pass ? 3 : 1] = q.R * (int64_t)(fine_pass ? q.Nf : q.Nc); }
+        return frc;
+    };
+    return walk_chunks(&p, 1, field, s);
 }
 
 }  // extern "C"

@@ -16,6 +16,7 @@ edges of the hot path:
     DEBUG is set -- it never changes outputs and costs a device sync per key;
   * autograd reaches the models' parameters and the rays (standard model, bf16 mode).
 """
+import collections
 import ctypes
 import os
 
@@ -30,6 +31,20 @@ from .nerf import NeRF
 DEBUG = False
 
 _KEYS_MAIN = ('rgb_map', 'disp_map', 'acc_map')
+_IO_OUT_KEYS = ('rgb_map', 'disp_map', 'acc_map', 'rgb0', 'disp0', 'acc0', 'z_std', 'raw', 'weights', 'z_vals')      # nerf_amd_render_io's outputs
+
+# The random draws of one render_rays call, in the reference's order (Renderer._draws).  A field is None where the reference
+# draws nothing; t_lin is the deterministic u as one cached row (it is not a draw and has no rows to slice).
+Draws = collections.namedtuple('Draws', 't_rand noise0 u noise1 t_lin')
+
+
+def _rows(x, i, j):
+    """Rows [i, j) of a tensor, of every tensor of an output dict or of a Draws record (None stays None)."""
+    if isinstance(x, dict):
+        return {k: v[i:j] for k, v in x.items()}
+    if isinstance(x, Draws):
+        return Draws(*[_rows(t, i, j) for t in x[:4]], x.t_lin)
+    return None if x is None else x[i:j]
 
 
 def _workspace(device, nbytes):
@@ -186,69 +201,93 @@ class Renderer(torch.nn.Module):
         hf = fine_model._model_handle(dev, copies) if use_fine else None
         return hc, hf, self._cfg(prec), lib.nerf_amd_model_out_ch(hc)
 
-    def _chunk_io(self, rays, cfg, out_ch, outs, pytest, ws=None, z_pre=None, t_rand_out=None):
-        """nerf_amd_render_io of one render_rays call on contiguous fp32 rays [R, 8|11] writing into the tensors
-        of ``outs`` (rows [0, R)): random draws in the reference's order and shapes (t_rand, noise0, u, noise1).
-        ws: workspace to use (default: a fresh one).  z_pre: this chunk's rows of a coarse-depth buffer that one
-        launch fills for all chunks afterwards; the jitter draws it needs go into t_rand_out (same rows).
-        Returns (io, tensors to keep alive)."""
-        R, dev = rays.shape[0], rays.device
-        Nc, Ni = int(self.N_samples), int(self.N_importance)
-        Nf = Nc + Ni
-        t_rand = noise0 = noise1 = u = None
-        if self.perturb > 0.:
-            if t_rand_out is not None:
-                t_rand_out.uniform_()        # the same draw as torch.rand([R, Nc]): rand() is empty().uniform_(0, 1)
-            else:
-                t_rand = _pytest_uniform([R, Nc], dev) if pytest else torch.rand([R, Nc], device=dev)
-        if self.raw_noise_std > 0.:
-            noise0 = (_pytest_uniform([R, Nc], dev) if pytest else torch.randn([R, Nc], device=dev)) * self.raw_noise_std
-        t_lin = None
-        if Ni > 0:
-            det = (self.perturb == 0.)
-            if pytest:
-                np.random.seed(0)
-                if det:
-                    u = np.broadcast_to(np.linspace(0., 1., Ni), [R, Ni])
-                else:
-                    u = np.random.rand(R, Ni)
-                u = torch.Tensor(np.ascontiguousarray(u)).to(dev)
-            elif det:
-                t_lin = _linspace01(Ni, dev)
-            else:
-                u = torch.rand([R, Ni], device=dev)
-            if self.raw_noise_std > 0.:
-                noise1 = (_pytest_uniform([R, Nf], dev) if pytest else torch.randn([R, Nf], device=dev)) * self.raw_noise_std
+    _UNFILLED = object()          # _draws(into=_UNFILLED): allocate what would be drawn, draw nothing (_draw_buffers)
 
+    def _draws(self, R, dev, pytest=False, into=None):
+        """The random draws of one render_rays call on R rays, as a Draws record.  The one place that knows the reference's
+        order, shapes and conditions: t_rand [R, Nc] under perturb, noise0 [R, Nc] under raw_noise_std, and with
+        N_importance > 0 u [R, Ni] (perturb == 0: nothing is drawn, t_lin is the cached linspace) and noise1 [R, Nc + Ni]
+        (render_utils.py:121,264, utils.py:86).  Two ways of producing them:
+          into=None     new tensors: torch.rand / torch.randn(...) * raw_noise_std, or with pytest=True the reference's seeded
+                        numpy draws (np.random.seed(0); np.random.rand(*shape) each; the deterministic u its broadcast linspace);
+          into=a Draws  of row slices [R, .] of the caller's buffers (_draw_buffers, _rows), filled in place: slice.uniform_() /
+                        slice.normal_() consume the generator exactly like torch.rand / torch.randn of the same shape.  The
+                        noise is left UNSCALED: the caller multiplies each whole buffer once (_scale_noise), not once per chunk."""
+        Nc, Ni, std = int(self.N_samples), int(self.N_importance), self.raw_noise_std
+        if into is self._UNFILLED:
+            uniform = normal = lambda name, shape: torch.empty(shape, device=dev, dtype=torch.float32)
+        elif into is not None:
+            uniform = lambda name, shape: getattr(into, name).uniform_()
+            normal = lambda name, shape: getattr(into, name).normal_()
+        elif pytest:
+            uniform = lambda name, shape: _pytest_uniform(shape, dev)
+            normal = lambda name, shape: _pytest_uniform(shape, dev) * std
+        else:
+            uniform = lambda name, shape: torch.rand(shape, device=dev)
+            normal = lambda name, shape: torch.randn(shape, device=dev) * std
+        jitter, noisy = self.perturb > 0., std > 0.
+        t_rand = uniform('t_rand', [R, Nc]) if jitter else None
+        noise0 = normal('noise0', [R, Nc]) if noisy else None
+        u = noise1 = t_lin = None
+        if Ni > 0:
+            if jitter:
+                u = uniform('u', [R, Ni])
+            elif pytest:
+                np.random.seed(0)
+                u = torch.Tensor(np.ascontiguousarray(np.broadcast_to(np.linspace(0., 1., Ni), [R, Ni]))).to(dev)
+            else:
+                t_lin = _linspace01(Ni, dev)
+            noise1 = normal('noise1', [R, Nc + Ni]) if noisy else None
+        return Draws(t_rand, noise0, u, noise1, t_lin)
+
+    def _draw_buffers(self, N, dev):
+        """Uninitialised buffers for the draws of N rays, for the in-place form of _draws to fill chunk by chunk."""
+        return self._draws(N, dev, into=self._UNFILLED)
+
+    def _scale_noise(self, bufs):
+        """What the in-place form of _draws leaves to its caller: raw_noise_std times each whole noise buffer, once."""
+        for t in (bufs.noise0, bufs.noise1):
+            if t is not None:
+                t.mul_(self.raw_noise_std)
+
+    def _io(self, rays, draws, outs, z_pre, ws, rows=None):
+        """The nerf_amd_render_io of one library call: contiguous fp32 rays [R, 8|11], their Draws record, the dict of output
+        tensors, coarse depths [R, N_samples] made in front (or None: the library makes them from t_rand) and the workspace.
+        rows=(i, j): the call covers rows [i, j) of all of these (the workspace is the call's own)."""
+        if rows is not None:
+            rays, draws, outs, z_pre = (_rows(x, *rows) for x in (rays, draws, outs, z_pre))
         io = _lib.RenderIO()
         io.rays, io.ray_ch = rays.data_ptr(), rays.shape[1]
-        io.t_vals = _linspace01(Nc, dev).data_ptr()
-        io.t_rand, io.noise0, io.noise1 = _lib.ptr(t_rand), _lib.ptr(noise0), _lib.ptr(noise1)
-        io.u, io.t_lin_imp = _lib.ptr(u), _lib.ptr(t_lin)
+        io.t_vals = _linspace01(int(self.N_samples), rays.device).data_ptr()
+        io.t_rand, io.noise0, io.u, io.noise1, io.t_lin_imp = (_lib.ptr(t) for t in draws)
         io.z_coarse = _lib.ptr(z_pre)
-        for k in ('rgb_map', 'disp_map', 'acc_map', 'rgb0', 'disp0', 'acc0', 'z_std', 'raw', 'weights', 'z_vals'):
+        for k in _IO_OUT_KEYS:
             setattr(io, k, _lib.ptr(outs.get(k)))
-        nbytes = lib.nerf_amd_render_rays_workspace(cfg, R, out_ch)
-        if ws is None or ws.numel() < nbytes:
-            ws = _workspace(dev, nbytes)
         io.workspace, io.workspace_bytes = ws.data_ptr(), ws.numel()
-        return io, (rays, t_rand, noise0, noise1, u, z_pre, ws)
+        return io
 
-    def _launch(self, rays, coarse_model, fine_model, outs, retraw, retweights, pytest):
+    def _chunk_inputs(self, rays, pytest):
+        """What one render_rays call prepares in front of the library: its draws, and with a coarse_sampler its coarse
+        depths (else None: the library computes the reference ladder itself)."""
+        R, dev = rays.shape[0], rays.device
+        draws, z_pre = self._draws(R, dev, pytest), None
+        if self.coarse_sampler is not None and R > 0:
+            z_pre = torch.empty(R, int(self.N_samples), device=dev, dtype=torch.float32)
+            with torch.cuda.device(dev):
+                self._coarse_z(rays, draws.t_rand, z_pre)
+        return draws, z_pre
+
+    def _launch(self, rays, coarse_model, fine_model, outs, pytest=False):
         """Enqueue render_rays for contiguous fp32 rays [R, 8|11]; writes into the
-        tensors of ``outs`` (rows [0, R))."""
+        tensors of ``outs`` (rows [0, R)).  The draws, depths and scratch it allocates go back to the caching allocator
+        on return: their reuse is ordered on the stream that is current, behind the launches that read them."""
         dev = rays.device
         hc, hf, cfg, out_ch = self._handles(dev, coarse_model, fine_model)
-        z_pre = None
-        if self.coarse_sampler is not None and rays.shape[0] > 0:
-            z_pre = torch.empty(rays.shape[0], int(self.N_samples), device=dev, dtype=torch.float32)
-        io, keep = self._chunk_io(rays, cfg, out_ch, outs, pytest, z_pre=z_pre)
+        draws, z_pre = self._chunk_inputs(rays, pytest)
+        ws = _workspace(dev, lib.nerf_amd_render_rays_workspace(cfg, rays.shape[0], out_ch))
+        io = self._io(rays, draws, outs, z_pre, ws)
         with torch.cuda.device(dev):
-            if z_pre is not None:
-                self._coarse_z(rays, keep[1], z_pre)                   # (keep[1]: the t_rand that _chunk_io drew)
             _lib.check(lib.nerf_amd_render_rays(cfg, hc, hf, io, rays.shape[0], _lib.stream_of(dev)), "nerf_amd_render_rays")
-        # keep the draws alive until the stream has consumed them (caching allocator is stream-ordered)
-        return keep
 
     # ------------------------------------------------------------------ occupancy grid (opt-in)
     occupancy = None              # a nerf_shared_amd.occupancy.OccupancyGrid: the no-grad render calls evaluate the field at
@@ -268,45 +307,29 @@ class Renderer(torch.nn.Module):
 
     def _launch_culled(self, rays, coarse_model, fine_model, outs, pytest, stats):
         """render_rays of one chunk's rays [R, 8|11] through nerf_amd_render_rays_culled into the rows of ``outs``: the
-        chunk's draws are made once, in the reference's order and shapes (as _chunk_io makes them), and the library is
-        called per group of at most CULL_GROUP_RAYS rays on the matching rows.  Adds the four counts to ``stats``."""
+        chunk's draws (and sampler depths) are made once, as _launch makes them, and the library is called per group of at
+        most CULL_GROUP_RAYS rays on the matching rows.  Adds the four counts to ``stats``."""
         dev, grid = rays.device, self.occupancy
         if grid.device != dev:
             raise _lib.NerfAmdError("Renderer.occupancy is on %s, the rays on %s" % (grid.device, dev))
         hc, hf, cfg, out_ch = self._handles(dev, coarse_model, fine_model)
-        R, Nc, Ni = rays.shape[0], int(self.N_samples), int(self.N_importance)
-        t_rand, _, _, u, t_lin = self._draws(R, dev, pytest)
-        z_pre = None
-        if self.coarse_sampler is not None and R > 0:
-            z_pre = torch.empty(R, Nc, device=dev, dtype=torch.float32)
-            with torch.cuda.device(dev):
-                self._coarse_z(rays, t_rand, z_pre)
+        R, step = rays.shape[0], self.CULL_GROUP_RAYS
+        draws, z_pre = self._chunk_inputs(rays, pytest)
         g = grid._c()
         counts = (ctypes.c_int64 * 4)()
-        step = self.CULL_GROUP_RAYS
         ws = _workspace(dev, lib.nerf_amd_render_rays_culled_workspace(cfg, min(R, step), out_ch))
         for i in range(0, R, step):
-            r = rays[i:i + step]
-            io = _lib.RenderIO()
-            io.rays, io.ray_ch = r.data_ptr(), r.shape[1]
-            io.t_vals = _linspace01(Nc, dev).data_ptr()
-            io.t_rand = None if t_rand is None else t_rand[i:i + step].data_ptr()
-            io.u = None if u is None else u[i:i + step].data_ptr()
-            io.t_lin_imp = _lib.ptr(t_lin)
-            io.z_coarse = None if z_pre is None else z_pre[i:i + step].data_ptr()
-            for k in ('rgb_map', 'disp_map', 'acc_map', 'rgb0', 'disp0', 'acc0', 'z_std', 'raw', 'weights', 'z_vals'):
-                v = outs.get(k)
-                setattr(io, k, None if v is None else v[i:i + step].data_ptr())
-            io.workspace, io.workspace_bytes = ws.data_ptr(), ws.numel()
+            j = min(i + step, R)
+            io = self._io(rays, draws, outs, z_pre, ws, rows=(i, j))
             with torch.cuda.device(dev):
-                _lib.check(lib.nerf_amd_render_rays_culled(cfg, hc, hf, io, r.shape[0], ctypes.byref(g), counts, _lib.stream_of(dev)),
+                _lib.check(lib.nerf_amd_render_rays_culled(cfg, hc, hf, io, j - i, ctypes.byref(g), counts, _lib.stream_of(dev)),
                            "nerf_amd_render_rays_culled")
-            for j, k in enumerate(('coarse_live', 'coarse_total', 'fine_live', 'fine_total')):
-                stats[k] += int(counts[j])
-        return (rays, t_rand, u, z_pre, ws)
+            for n, k in enumerate(stats):
+                stats[k] += int(counts[n])
+
 
     @staticmethod
-    def _new_cull_stats():
+    def _new_cull_stats():          # in the order of nerf_amd_render_rays_culled's four counts
         return {'coarse_live': 0, 'coarse_total': 0, 'fine_live': 0, 'fine_total': 0}
 
     # ------------------------------------------------------------------ occupancy grid in training and pose estimation (opt-in)
@@ -383,113 +406,83 @@ class Renderer(torch.nn.Module):
                                          rays.shape[0], Nc, int(bool(self.lindisp)), int(self.perturb > 0.), z_out.data_ptr(),
                                          _lib.stream_of(dev)), "nerf_amd_coarse_z")
 
-    def _launch_batch(self, rays, starts, chunk, coarse_model, fine_model, full):
-        """render_batch as ONE library call over whole-batch buffers (nerf_amd_render_batch).  The random draws are made
-        per chunk, in the reference's order (t_rand, noise0, u, noise1 of chunk 0, then of chunk 1, ...), into the rows of
-        one buffer each -- `slice.uniform_()` / `slice.normal_()` consume the generator exactly like the reference's
-        torch.rand / torch.randn of the same shape -- so the result equals per-chunk render_rays calls bit for bit, while
+    def _draw_chunks(self, N, dev, spans):
+        """The draws of every chunk of a batch in whole-batch buffers: the reference's order inside every render_rays call
+        (t_rand, noise0, u, noise1 of chunk 0, then of chunk 1, ...), each into its rows of one buffer per kind, so the
+        result equals per-chunk render_rays calls bit for bit."""
+        bufs = self._draw_buffers(N, dev)
+        for i, j in spans:
+            self._draws(j - i, dev, into=_rows(bufs, i, j))
+        self._scale_noise(bufs)
+        return bufs
+
+    def _launch_batch(self, rays, spans, coarse_model, fine_model, full):
+        """render_batch as ONE library call over whole-batch buffers (nerf_amd_render_batch), draws per chunk (_draw_chunks):
         the library is free to launch in groups that suit the GPU and to run the per-ray kernels beside the field kernels."""
-        dev = rays.device
+        dev, N = rays.device, rays.shape[0]
         hc, hf, cfg, out_ch = self._handles(dev, coarse_model, fine_model)
-        N, Nc, Ni = rays.shape[0], int(self.N_samples), int(self.N_importance)
-        f = dict(device=dev, dtype=torch.float32)
-        z_all = torch.empty(N, Nc, **f)
-        noisy = self.raw_noise_std > 0.
-        t_all = n0_all = n1_all = u_all = None
-        if self.perturb > 0. or noisy:
+        z_all = torch.empty(N, int(self.N_samples), device=dev, dtype=torch.float32)
+        if self.perturb > 0. or self.raw_noise_std > 0.:
             # The draws depend on nothing but the generator (whose state lives on the host), so they go on a stream of
             # their own: the dozens of small RNG launches of this call then run beside whatever the device is still busy
             # with (the field kernels of the previous frame, when frames are rendered back to back) instead of in front
             # of this frame's first field kernel.  Same values as on the caller's stream.
             cur, ds = torch.cuda.current_stream(dev), _draw_stream(dev)
             with torch.cuda.stream(ds):
-                t_all = torch.empty(N, Nc, **f) if self.perturb > 0. else None
-                n0_all = torch.empty(N, Nc, **f) if noisy else None
-                n1_all = torch.empty(N, Nc + Ni, **f) if (noisy and Ni > 0) else None
-                u_all = torch.empty(N, Ni, **f) if (Ni > 0 and self.perturb > 0.) else None
-                for i in starts:                               # the reference's order inside every render_rays call
-                    if t_all is not None:
-                        t_all[i:i + chunk].uniform_()
-                    if n0_all is not None:
-                        n0_all[i:i + chunk].normal_()
-                    if u_all is not None:
-                        u_all[i:i + chunk].uniform_()
-                    if n1_all is not None:
-                        n1_all[i:i + chunk].normal_()
-                if noisy:
-                    n0_all.mul_(self.raw_noise_std)
-                    if n1_all is not None:
-                        n1_all.mul_(self.raw_noise_std)
+                bufs = self._draw_chunks(N, dev, spans)
                 drawn = torch.cuda.Event()
                 drawn.record(ds)
             cur.wait_event(drawn)
-            for t in (t_all, n0_all, n1_all, u_all):           # allocated on the draw stream, consumed on the caller's
+            for t in bufs[:4]:                                 # allocated on the draw stream, consumed on the caller's
                 if t is not None:
                     t.record_stream(cur)
-        io = _lib.RenderIO()
-        io.rays, io.ray_ch = rays.data_ptr(), rays.shape[1]
-        io.t_vals = _linspace01(Nc, dev).data_ptr()
-        io.t_rand, io.noise0, io.noise1, io.u = _lib.ptr(t_all), _lib.ptr(n0_all), _lib.ptr(n1_all), _lib.ptr(u_all)
-        io.t_lin_imp = _linspace01(Ni, dev).data_ptr() if (Ni > 0 and u_all is None) else None
-        io.z_coarse = z_all.data_ptr()
-        for k in ('rgb_map', 'disp_map', 'acc_map', 'rgb0', 'disp0', 'acc0', 'z_std', 'raw', 'weights', 'z_vals'):
-            setattr(io, k, _lib.ptr(full.get(k)))
+        else:
+            bufs = self._draws(N, dev)                         # nothing to draw: the deterministic u, if any
         ws = _workspace(dev, lib.nerf_amd_render_batch_workspace(cfg, N, out_ch))
-        io.workspace, io.workspace_bytes = ws.data_ptr(), ws.numel()
+        io = self._io(rays, bufs, full, z_all, ws)
         with torch.cuda.device(dev):
-            self._coarse_z(rays, t_all, z_all)
+            self._coarse_z(rays, bufs.t_rand, z_all)
+            # the library's side stream reads the buffers too; its work is ordered before the caller's stream continues, so
+            # releasing them to the caching allocator (stream-ordered on the caller's stream) on return is safe
             _lib.check(lib.nerf_amd_render_batch(cfg, hc, hf, io, N, _lib.stream_of(dev)), "nerf_amd_render_batch")
-        # the library's side stream reads these too; its work is ordered before the caller's stream continues, so
-        # releasing them to the caching allocator (stream-ordered on the caller's stream) is safe
-        return (rays, z_all, t_all, n0_all, n1_all, u_all, ws)
 
-    def _launch_chunks(self, rays, starts, chunk, coarse_model, fine_model, full):
-        """render_batch's chunk loop as one library call (nerf_amd_render_chunks): per-chunk draws (in the
-        reference's per-chunk order) and output rows exactly as _launch makes them, two workspaces used
-        alternately, and the coarse depths of all chunks from one launch in front."""
-        dev = rays.device
+    def _launch_chunks(self, rays, spans, coarse_model, fine_model, full):
+        """render_batch's chunk loop as one library call (nerf_amd_render_chunks): per-chunk draws (_draw_chunks) and
+        output rows exactly as _launch makes them, two workspaces used alternately, and the coarse depths of all chunks
+        from one launch in front."""
+        dev, N, n = rays.device, rays.shape[0], len(spans)
         hc, hf, cfg, out_ch = self._handles(dev, coarse_model, fine_model)
-        n, N, Nc = len(starts), rays.shape[0], int(self.N_samples)
-        ios = (_lib.RenderIO * n)()
-        counts = (ctypes.c_int64 * n)()
-        keep = []
-        z_all = torch.empty(N, Nc, device=dev, dtype=torch.float32)
-        t_all = torch.empty(N, Nc, device=dev, dtype=torch.float32) if self.perturb > 0. else None
-        nbytes = lib.nerf_amd_render_rays_workspace(cfg, min(chunk, N), out_ch)
+        z_all = torch.empty(N, int(self.N_samples), device=dev, dtype=torch.float32)
+        bufs = self._draw_chunks(N, dev, spans)
+        nbytes = lib.nerf_amd_render_rays_workspace(cfg, max(j - i for i, j in spans), out_ch)
         wss = [_workspace(dev, nbytes), _workspace(dev, nbytes)]
-        for j, i in enumerate(starts):
-            part = {k: v[i:i + chunk] for k, v in full.items()}
-            r = rays[i:i + chunk]
-            ios[j], alive = self._chunk_io(r, cfg, out_ch, part, False, wss[j % 2], z_all[i:i + chunk],
-                                           None if t_all is None else t_all[i:i + chunk])
-            counts[j] = r.shape[0]
-            keep.append(alive)
+        ios = (_lib.RenderIO * n)(*[self._io(rays, bufs, full, z_all, wss[k % 2], rows=s) for k, s in enumerate(spans)])
+        counts = (ctypes.c_int64 * n)(*[j - i for i, j in spans])
         with torch.cuda.device(dev):
-            self._coarse_z(rays, t_all, z_all)
+            self._coarse_z(rays, bufs.t_rand, z_all)
             _lib.check(lib.nerf_amd_render_chunks(cfg, hc, hf, ios, counts, n, _lib.stream_of(dev)), "nerf_amd_render_chunks")
-        return keep
 
-    def _draws(self, R, dev, pytest):
-        """Random draws of one render_rays call in the reference's order and shapes."""
-        Nc, Ni = int(self.N_samples), int(self.N_importance)
-        t_rand = noise0 = noise1 = u = t_lin = None
-        if self.perturb > 0.:
-            t_rand = _pytest_uniform([R, Nc], dev) if pytest else torch.rand([R, Nc], device=dev)
-        if self.raw_noise_std > 0.:
-            noise0 = (_pytest_uniform([R, Nc], dev) if pytest else torch.randn([R, Nc], device=dev)) * self.raw_noise_std
-        if Ni > 0:
-            det = (self.perturb == 0.)
-            if pytest:
-                np.random.seed(0)
-                un = np.broadcast_to(np.linspace(0., 1., Ni), [R, Ni]) if det else np.random.rand(R, Ni)
-                u = torch.Tensor(np.ascontiguousarray(un)).to(dev)
-            elif det:
-                t_lin = _linspace01(Ni, dev)
-            else:
-                u = torch.rand([R, Ni], device=dev)
-            if self.raw_noise_std > 0.:
-                noise1 = (_pytest_uniform([R, Nc + Ni], dev) if pytest else torch.randn([R, Nc + Ni], device=dev)) * self.raw_noise_std
-        return t_rand, noise0, noise1, u, t_lin
+    def _launch_overlapped(self, rays, spans, coarse_model, fine_model, full):
+        """render_batch's chunk loop with consecutive chunks alternating between two side streams (overlap_chunks)."""
+        dev = rays.device
+        # pack parameters and build the cached linspaces on the caller's stream first, then fan out
+        _linspace01(int(self.N_samples), dev)
+        if self.N_importance > 0:
+            _linspace01(int(self.N_importance), dev)
+        self._handles(dev, coarse_model, fine_model)
+        cur = torch.cuda.current_stream(dev)
+        ready = torch.cuda.Event()
+        ready.record(cur)
+        side = _chunk_streams(dev)
+        for s in side:
+            s.wait_event(ready)
+        for n, (i, j) in enumerate(spans):
+            with torch.cuda.stream(side[n % len(side)]):      # draws and scratch are made on the chunk's own stream
+                self._launch(rays[i:j], coarse_model, fine_model, _rows(full, i, j))
+        for s in side:
+            cur.wait_stream(s)
+        for v in full.values():
+            v.record_stream(side[0]); v.record_stream(side[1])
 
     def _render_rays_train(self, rays, coarse_model, fine_model, retraw, retweights, pytest):
         """render_rays with autograd into the models' parameters (what main.py:77-104 needs):
@@ -499,7 +492,7 @@ class Renderer(torch.nn.Module):
         (render_utils.py:145); `rays` may require grad (pose estimation)."""
         R, dev = rays.shape[0], rays.device
         Nc, Ni = int(self.N_samples), int(self.N_importance)
-        t_rand, noise0, noise1, u, t_lin = self._draws(R, dev, pytest)
+        t_rand, noise0, u, noise1, t_lin = self._draws(R, dev, pytest)
         f = dict(device=dev, dtype=torch.float32)
         stream = _lib.stream_of(dev)
         z = torch.empty(R, Nc, **f)
@@ -543,7 +536,7 @@ class Renderer(torch.nn.Module):
         if retraw:
             ret['raw'] = raw
         if retweights:
-            ret['weights'] = weights if z.shape[1] > 1 else weights[:, :0]     # one sample: see raw2outputs
+            ret['weights'] = weights
             ret['z_vals'] = z
         if Ni > 0:
             ret.update(rgb0=rgb0, disp0=disp0, acc0=acc0, z_std=z_std)
@@ -585,39 +578,7 @@ class Renderer(torch.nn.Module):
         Returns the reference's dict: rgb_map, disp_map, acc_map, [raw],
         [weights, z_vals], and with N_importance > 0: rgb0, disp0, acc0, z_std.
         """
-        return self._render_rays(self._clip(ray_batch), coarse_model, fine_model, retraw, retweights, verbose, pytest)
-
-    def _render_rays(self, ray_batch, coarse_model, fine_model, retraw=False, retweights=False, verbose=False, pytest=False):
-        """render_rays behind the ray-bounds clip (render_batch, which has clipped its whole batch, calls this per chunk)."""
-        _lib.require_device(ray_batch, "ray_batch")
-        coarse_model, fine_model = nerf_mod.adopt(coarse_model), nerf_mod.adopt(fine_model)     # reference-class models: a twin sharing their parameters
-        rays = ray_batch.detach().contiguous().float()
-        if rays.dim() != 2 or rays.shape[1] not in (8, 11):
-            raise _lib.NerfAmdError("ray_batch must be [N, 8] or [N, 11], got %s" % (tuple(ray_batch.shape),))
-        self._check_model(coarse_model, "coarse_model")
-        if fine_model is not None:
-            self._check_model(fine_model, "fine_model")
-        self._check_sampler(rays.device)
-        mode, deferred = self._grad_mode(coarse_model, fine_model, ray_batch) if rays.shape[0] > 0 else ("none", None)
-        if self.occupancy is not None:
-            self._check_cullable(mode)
-            out_ch = 4 if coarse_model.use_viewdirs else coarse_model.output_ch
-            outs = self._alloc_outputs(rays.shape[0], rays.device, out_ch, retraw, retweights)
-            stats = self._new_cull_stats()
-            self._launch_culled(rays, coarse_model, fine_model, outs, pytest, stats)
-            self.last_cull = stats
-            if retweights and outs['weights'].shape[1] == 1:
-                outs['weights'] = outs['weights'][:, :0]                       # one sample: see raw2outputs
-            return outs
-        if mode == "train":
-            live = ray_batch.contiguous().float() if (torch.is_grad_enabled() and ray_batch.requires_grad) else rays
-            return self._render_rays_train(live, coarse_model, fine_model, retraw, retweights, pytest)
-        out_ch = 4 if coarse_model.use_viewdirs else coarse_model.output_ch
-        outs = self._alloc_outputs(rays.shape[0], rays.device, out_ch, retraw, retweights)
-        self._launch(rays, coarse_model, fine_model, outs, retraw, retweights, pytest)
-        if retweights and outs['weights'].shape[1] == 1:
-            outs['weights'] = outs['weights'][:, :0]                           # one sample: see raw2outputs
-        ret = nerf_mod.attach_deferred_grad(outs, deferred)
+        ret = self._render("ray_batch", self._clip(ray_batch), coarse_model, fine_model, None, retraw, retweights, pytest)
         if DEBUG:
             for k in ret:
                 if torch.isnan(ret[k]).any() or torch.isinf(ret[k]).any():
@@ -642,73 +603,54 @@ class Renderer(torch.nn.Module):
         of the other; results do not depend on it (random draws come from the device's one
         generator in chunk order in every mode).  Off by default: the gain is ~3 % and
         concurrent kernels blur per-kernel timings."""
-        return self._render_batch(coarse_model, fine_model, self._clip(rays_flat), chunk, retraw)
+        return self._render("rays_flat", self._clip(rays_flat), coarse_model, fine_model, chunk, retraw)
 
-    def _render_batch(self, coarse_model, fine_model, rays_flat, chunk, retraw):
-        """render_batch behind the ray-bounds clip."""
-        _lib.require_device(rays_flat, "rays_flat")
-        coarse_model, fine_model = nerf_mod.adopt(coarse_model), nerf_mod.adopt(fine_model)
-        rays = rays_flat.detach().contiguous().float()
+    def _render(self, name, ray_batch, coarse_model, fine_model, chunk, retraw, retweights=False, pytest=False):
+        """render_rays and render_batch behind the ray-bounds clip: one preamble and one statement of the choice between
+        the culled, the training and the dense path (a deferred gradient: the dense path, with a backward that explains
+        itself, nerf._grad_request).  Every path works chunk by chunk, a chunk being one render_rays call of the
+        reference with its own draws.  chunk=None is render_rays: the batch, empty or not, is the one chunk; it is passed on
+        unsliced and always goes to the library as one nerf_amd_render_rays call."""
+        _lib.require_device(ray_batch, name)
+        coarse_model, fine_model = nerf_mod.adopt(coarse_model), nerf_mod.adopt(fine_model)     # reference-class models: a twin sharing their parameters
+        rays = ray_batch.detach().contiguous().float()
+        if rays.dim() != 2 or rays.shape[1] not in (8, 11):
+            raise _lib.NerfAmdError("%s must be [N, 8] or [N, 11], got %s" % (name, tuple(ray_batch.shape)))
         self._check_model(coarse_model, "coarse_model")
+        if fine_model is not None:
+            self._check_model(fine_model, "fine_model")
         N, dev = rays.shape[0], rays.device
         self._check_sampler(dev)
+        mode, deferred = self._grad_mode(coarse_model, fine_model, ray_batch) if N > 0 else ("none", None)
         out_ch = 4 if coarse_model.use_viewdirs else coarse_model.output_ch
-        starts = list(range(0, N, chunk))
-        mode, deferred = self._grad_mode(coarse_model, fine_model, rays_flat) if N > 0 else ("none", None)
+        spans = [(0, N)] if chunk is None else [(i, min(i + chunk, N)) for i in range(0, N, chunk)]
         if self.occupancy is not None:     # per chunk (the reference's draws), the library called per group of <= 32768 rays
             self._check_cullable(mode)
-            full = self._alloc_outputs(N, dev, out_ch, retraw, False)
+            ret = self._alloc_outputs(N, dev, out_ch, retraw, retweights)
             stats = self._new_cull_stats()
-            for i in starts:
-                part = {k: v[i:i + chunk] for k, v in full.items()}
-                self._launch_culled(rays[i:i + chunk], coarse_model, fine_model, part, False, stats)
+            for i, j in spans:
+                self._launch_culled(rays[i:j], coarse_model, fine_model, _rows(ret, i, j), pytest, stats)
             self.last_cull = stats
-            return full
-        if mode == "defer":            # forward-only kernels now, a backward that explains itself later (nerf._grad_request)
-            with torch.no_grad():
-                plain = self._render_batch(coarse_model, fine_model, rays_flat, chunk, retraw)
-            return nerf_mod.attach_deferred_grad(plain, deferred)
-        if mode == "train":
-            live = rays_flat if (torch.is_grad_enabled() and rays_flat.requires_grad) else rays
-            parts = {}                     # training: autograd graph per chunk, concatenated like the reference
-            for i in starts:
-                r = self._render_rays(live[i:i + chunk], coarse_model, fine_model, retraw)
-                for k, v in r.items():
-                    parts.setdefault(k, []).append(v)
-            # (one chunk: the reference's torch.cat of a single tensor is a copy of it)
-            return {k: (v[0] if len(v) == 1 else torch.cat(v, 0)) for k, v in parts.items()}
-        full = self._alloc_outputs(N, dev, out_ch, retraw, False)
-        if self.pipeline_batch and N > 0 and (len(starts) > 1 or N > 49152):
-            self._launch_batch(rays, starts, chunk, coarse_model, fine_model, full)
-            return full
-        if not (self.overlap_chunks and len(starts) > 1):
-            if len(starts) > 1 and self.fuse_chunk_launches:
-                self._launch_chunks(rays, starts, chunk, coarse_model, fine_model, full)
-                return full
-            for i in starts:
-                part = {k: v[i:i + chunk] for k, v in full.items()}
-                self._launch(rays[i:i + chunk], coarse_model, fine_model, part, retraw, False, False)
-            return full
-        # pack parameters and build the cached linspaces on the caller's stream first, then fan out
-        _linspace01(int(self.N_samples), dev)
-        if self.N_importance > 0:
-            _linspace01(int(self.N_importance), dev)
-        self._handles(dev, coarse_model, fine_model)
-        cur = torch.cuda.current_stream(dev)
-        ready = torch.cuda.Event()
-        ready.record(cur)
-        side = _chunk_streams(dev)
-        for s in side:
-            s.wait_event(ready)
-        for n, i in enumerate(starts):
-            with torch.cuda.stream(side[n % len(side)]):      # draws and scratch are made on the chunk's own stream
-                part = {k: v[i:i + chunk] for k, v in full.items()}
-                self._launch(rays[i:i + chunk], coarse_model, fine_model, part, retraw, False, False)
-        for s in side:
-            cur.wait_stream(s)
-        for v in full.values():
-            v.record_stream(side[0]); v.record_stream(side[1])
-        return full
+        elif mode == "train":              # an autograd graph per chunk, concatenated like the reference
+            live = ray_batch if (torch.is_grad_enabled() and ray_batch.requires_grad) else rays
+            parts = [self._render_rays_train((live if chunk is None else live[i:j]).contiguous().float(), coarse_model,
+                                             fine_model, retraw, retweights, pytest) for i, j in spans]
+            # (one chunk: the tensors themselves -- the reference's torch.cat of a single tensor is a copy of it)
+            ret = parts[0] if len(parts) == 1 else {k: torch.cat([p[k] for p in parts], 0) for k in parts[0]}
+        else:
+            ret = self._alloc_outputs(N, dev, out_ch, retraw, retweights)
+            if chunk is not None and self.pipeline_batch and N > 0 and (len(spans) > 1 or N > 49152):
+                self._launch_batch(rays, spans, coarse_model, fine_model, ret)
+            elif len(spans) > 1 and self.overlap_chunks:
+                self._launch_overlapped(rays, spans, coarse_model, fine_model, ret)
+            elif len(spans) > 1 and self.fuse_chunk_launches:
+                self._launch_chunks(rays, spans, coarse_model, fine_model, ret)
+            else:
+                for i, j in spans:
+                    self._launch(rays[i:j], coarse_model, fine_model, _rows(ret, i, j), pytest)
+        if retweights and ret['weights'].shape[1] == 1:
+            ret['weights'] = ret['weights'][:, :0]                             # one sample: see raw2outputs
+        return nerf_mod.attach_deferred_grad(ret, deferred)
 
     def render(self, H, W, K, coarse_model, fine_model, chunk=1024 * 32, rays=None, retraw=True,
                c2w=None, c2w_staticcam=None):

@@ -268,14 +268,16 @@ def test_render_rays_with_the_hook_is_the_library_call_fed_the_depths_by_hand(de
         got = a.render_rays(rays, mc, mf, retraw=True, retweights=True)
         torch.manual_seed(9)
         plain = b.render_rays(rays, mc, mf, retraw=True, retweights=True)
-        # by hand: the draws of one render_rays call (Renderer._chunk_io makes them in the reference's order), the depths from
+        # by hand: the draws of one render_rays call (Renderer._draws makes them in the reference's order), the depths from
         # the public OccupancyGrid.coarse_depths on the jitter draws, and the library's render_rays on io.z_coarse
         torch.manual_seed(9)
         hc, hf, cfg, out_ch = b._handles(dev, mc, mf)
         outs = b._alloc_outputs(R, dev, out_ch, True, True)
         z_hand = torch.empty(R, NC, device=dev)
-        io, keep = b._chunk_io(rays, cfg, out_ch, outs, False, z_pre=z_hand)
-        t_rand = keep[1]
+        draws = b._draws(R, dev)
+        ws = render_utils._workspace(dev, lib.nerf_amd_render_rays_workspace(cfg, R, out_ch))
+        io = b._io(rays, draws, outs, z_hand, ws)
+        t_rand = draws.t_rand
         assert t_rand.shape == (R, NC) and io.z_coarse == z_hand.data_ptr()
         z, L = grid.coarse_depths(rays, render_utils._linspace01(NC, dev), PROBES, PAD, t_rand=t_rand)
         z_hand.copy_(z)

@@ -1084,6 +1084,63 @@ def test_seeded_multichunk_render_equals_per_chunk_render_rays(dev):
     assert not torch.equal(other["rgb_map"], want["rgb_map"])
 
 
+def test_every_render_path_consumes_the_generator_like_the_reference(dev):
+    """Seed, run a path, read the device generator's state: it is the state after the same seed and the reference's own
+    draws (torch.rand [R, Nc], torch.randn [R, Nc] * std, torch.rand [R, Ni], torch.randn [R, Nc + Ni] * std, each only where
+    the reference draws it) -- once for a render_rays call, once per chunk (16, 16, 5 rows) for render_batch -- on every
+    path: no-grad, training and culled render_rays, render_batch in its four modes, culled render_batch."""
+    _, render_utils, utils = amd()
+    from nerf_shared_amd import occupancy
+    N, Nc, Ni, chunk = 37, 8, 8, 16
+    K = synth.lego_intrinsics(400, 400)
+    batch = utils.make_ray_batch(400, 400, K, synth.LEGO_C2W, 2.0, 6.0, True, False, device=dev, pix0=70000, n=N)
+    c, f = gpu_model(dev, 1, 3.0, "bf16", **VD), gpu_model(dev, 19, 3.0, "bf16", **VD)
+    ct, ft = gpu_model(dev, 1, 3.0, "bf16", **VD).requires_grad_(True), gpu_model(dev, 19, 3.0, "bf16", **VD).requires_grad_(True)
+    grid = occupancy.OccupancyGrid([[-16.0] * 3, [16.0] * 3], 4, device=dev)        # a new grid is all live
+    R = render_utils.Renderer
+
+    def state_after(rows, std):
+        torch.manual_seed(21)
+        for n in rows:
+            torch.rand([n, Nc], device=dev)
+            if std > 0.:
+                torch.randn([n, Nc], device=dev) * std
+            torch.rand([n, Ni], device=dev)
+            if std > 0.:
+                torch.randn([n, Nc + Ni], device=dev) * std
+        return torch.cuda.get_rng_state(dev)
+
+    def state_of(run):
+        torch.manual_seed(21)
+        run()
+        torch.cuda.synchronize()
+        return torch.cuda.get_rng_state(dev)
+
+    modes = {"pipeline_batch": (True, True, False), "fused": (False, True, False), "per_chunk": (False, False, False),
+             "overlap": (False, True, True)}
+    for std in (0.0, 0.5):
+        r = R(**dict(BASE, perturb=1.0, N_samples=Nc, N_importance=Ni, raw_noise_std=std))
+        assert r._grad_mode(ct, ft, batch)[0] == "train" and r._grad_mode(c, f, batch)[0] == "none"
+        once, per_chunk = state_after([N], std), state_after([16, 16, 5], std)
+        assert not torch.equal(once, per_chunk) and not torch.equal(once, state_after([], std))
+        with torch.no_grad():
+            assert torch.equal(state_of(lambda: r.render_rays(batch, c, f)), once), ("render_rays", std)
+        assert torch.equal(state_of(lambda: r.render_rays(batch, ct, ft)), once), ("train", std)
+        try:
+            for name, (pipe, fuse, overlap) in modes.items():
+                R.pipeline_batch, R.fuse_chunk_launches, R.overlap_chunks = pipe, fuse, overlap
+                with torch.no_grad():
+                    assert torch.equal(state_of(lambda: r.render_batch(c, f, batch, chunk=chunk)), per_chunk), (name, std)
+        finally:
+            R.pipeline_batch, R.fuse_chunk_launches, R.overlap_chunks = True, True, False
+        if std == 0.0:                                                # (the culled path refuses noise: test_gpu_occupancy)
+            r.occupancy = grid
+            with torch.no_grad():
+                assert torch.equal(state_of(lambda: r.render_rays(batch, c, f)), once), "culled render_rays"
+                assert r.last_cull["coarse_live"] == r.last_cull["coarse_total"] == N * Nc
+                assert torch.equal(state_of(lambda: r.render_batch(c, f, batch, chunk=chunk)), per_chunk), "culled render_batch"
+
+
 def test_pipelined_batch_over_several_launch_groups(dev):
     """nerf_amd_render_batch: 100 000 rays = three full 32768-ray launch groups and a ragged fourth, per-ray kernels on the
     library's side stream.  Every output equals the chunk-at-a-time path bit for bit -- deterministic, with random draws

@@ -685,3 +685,72 @@ def test_reference_class_models_are_adopted_by_sharing_their_parameters():
     with pytest.raises(TypeError, match="layer shapes"):
         nerf.adopt(bad)
     assert nerf.adopt(None) is None
+
+
+def _reference_draws(R, Nc, Ni, perturb, std, dev):
+    """The reference's draws of one render_rays call, restated literally: order, shapes and conditions of
+    render_utils.py:121,264 and utils.py:86."""
+    t_rand = torch.rand([R, Nc], device=dev) if perturb > 0. else None
+    noise0 = torch.randn([R, Nc], device=dev) * std if std > 0. else None
+    u = torch.rand([R, Ni], device=dev) if (Ni > 0 and perturb > 0.) else None
+    noise1 = torch.randn([R, Nc + Ni], device=dev) * std if (Ni > 0 and std > 0.) else None
+    return t_rand, noise0, u, noise1
+
+
+def _same_bits(a, b):
+    if a is None or b is None:
+        return a is None and b is None
+    return a.dtype == b.dtype == torch.float32 and a.shape == b.shape and torch.equal(a.contiguous().view(torch.int32), b.contiguous().view(torch.int32))
+
+
+_DRAW_CASES = [(R, Nc, Ni, p, s) for (R, Nc, Ni) in ((5, 3, 1), (37, 8, 8), (5, 3, 0), (37, 8, 0)) for p in (0.0, 1.0) for s in (0.0, 0.5)]
+
+
+@pytest.mark.parametrize("R,Nc,Ni,perturb,std", _DRAW_CASES)
+def test_the_draw_routine_is_the_reference_restated(R, Nc, Ni, perturb, std):
+    """Renderer._draws against a literal restatement of the reference, on the CPU generator: the allocating form, the
+    pytest=True numpy form, and the in-place form over ragged chunks."""
+    cpu = torch.device("cpu")
+    r = render_utils.Renderer(perturb=perturb, N_importance=Ni, N_samples=Nc, raw_noise_std=std, near=2.0, far=6.0)
+    torch.manual_seed(3)
+    want = _reference_draws(R, Nc, Ni, perturb, std, cpu)
+    torch.manual_seed(3)
+    got = r._draws(R, cpu)
+    assert type(got).__name__ == "Draws" and got._fields == ("t_rand", "noise0", "u", "noise1", "t_lin")
+    for name, w in zip(got._fields, want):
+        assert _same_bits(getattr(got, name), w), name
+    if perturb == 0.0 and Ni > 0:
+        assert got.u is None and _same_bits(got.t_lin, torch.linspace(0., 1., Ni))
+    else:
+        assert got.t_lin is None
+
+    def numpy_draw(shape):
+        np.random.seed(0)
+        return torch.Tensor(np.random.rand(*shape))
+
+    py = r._draws(R, cpu, pytest=True)
+    assert _same_bits(py.t_rand, numpy_draw([R, Nc]) if perturb > 0. else None)
+    assert _same_bits(py.noise0, numpy_draw([R, Nc]) * std if std > 0. else None)
+    assert _same_bits(py.noise1, numpy_draw([R, Nc + Ni]) * std if (std > 0. and Ni > 0) else None)
+    assert py.t_lin is None
+    if Ni == 0:
+        assert py.u is None
+    elif perturb > 0.:
+        assert _same_bits(py.u, numpy_draw([R, Ni]))
+    else:
+        assert _same_bits(py.u, torch.Tensor(np.ascontiguousarray(np.broadcast_to(np.linspace(0., 1., Ni), [R, Ni]))))
+
+    # in place, chunk by chunk (16 + 16 + 5 of 37 rows), into buffers whose first 4 rows belong to nobody
+    spans = [(i, min(i + 16, R)) for i in range(0, R, 16)]
+    torch.manual_seed(4)
+    want = [r._draws(j - i, cpu) for i, j in spans]
+    torch.manual_seed(4)
+    bufs = r._draw_buffers(R + 4, cpu)
+    for i, j in spans:
+        r._draws(j - i, cpu, into=render_utils._rows(bufs, 4 + i, 4 + j))
+    r._scale_noise(bufs)
+    for (i, j), w in zip(spans, want):
+        part = render_utils._rows(bufs, 4 + i, 4 + j)
+        for name in ("t_rand", "noise0", "u", "noise1"):
+            assert _same_bits(getattr(part, name), getattr(w, name)), (name, i)
+        assert _same_bits(part.t_lin, w.t_lin)
