@@ -740,7 +740,13 @@ int nerf_amd_profile_enable(int on);
  *        0 = default: in the no-grad render path (nerf_amd_render_batch and the render calls built on the same stages);
  *            nerf_amd_nerf_forward stays unfolded and bit-equal to the training forward;
  *        1 = nowhere (A/B leg: the unfolded kernels everywhere);
- *        2 = in nerf_amd_nerf_forward too (tests, tools/mlp_ab.py). */
+ *        2 = in nerf_amd_nerf_forward too (tests, tools/mlp_ab.py).
+ * key 3: the colour branch (views_linears.0, rgb) of 16-sample blocks whose sigmas are all <= 0, in the folded render kernels:
+ *        0 = default: not computed where a render hands out no raw and adds no sigma noise (nerf_amd_render_rays / _chunks /
+ *            _batch with io->raw, io->noise0 and io->noise1 NULL and use_noise 0): such samples have weight exactly 0, the maps
+ *            are bit-identical; everything else (raw to the caller, noise, nerf_amd_nerf_forward, nerf_amd_field_points, the
+ *            culled renders, training, density queries, fp32 and fp32_split) computes every sample;
+ *        1 = never (A/B leg). */
 int nerf_amd_set_tuning(int key, int value);
 int nerf_amd_profile_collect(int64_t launches[3], double total_ms[3], double total_points[3]);
 

@@ -69,6 +69,9 @@ std::atomic<int> g_variant{0};
 // nerf_amd_set_tuning key 2: where bf16 view-branch models run the folded stream (feature_linear folded into views_linears.0):
 // 0 the no-grad render path, 1 nowhere, 2 nerf_amd_nerf_forward too
 std::atomic<int> g_fold{0};
+// nerf_amd_set_tuning key 3: the colour branch of sample blocks without density in the folded render kernels (MlpArgs::view_skip):
+// 0 skipped where the render allows it (stage_field), 1 never (the A/B leg: every point runs the full instruction path)
+std::atomic<int> g_view_skip_off{0};
 
 int tile_counters_init(int device) {
     if (device < 0 || device >= 16) return NERF_AMD_EINVAL;
@@ -799,6 +802,10 @@ int stage_field(const ChunkPlan &p, bool fine_pass, hipStream_t s) {
     MlpArgs a{};
     set_inputs(a, nullptr, nullptr, p.io->rays, p.io->ray_ch, fine_pass ? p.z_f : p.z_c, p.has_vd);
     a.S = fine_pass ? p.Nf : p.Nc; a.P = p.R * (int64_t)a.S; a.out = fine_pass ? p.raw_f : p.raw_c;
+    // raw2outputs gives a sample with sigma <= 0 the weight 1 - exp(-0) = 0 exactly, so its rgb reaches every map as + 0 whatever
+    // (finite) value it has -- unless the caller gets raw itself, or noise is added to sigma first (sigma + noise has its own sign)
+    a.view_skip = !p.io->raw && !p.cfg->use_noise && !p.io->noise0 && !p.io->noise1 &&
+                  g_view_skip_off.load(std::memory_order_relaxed) == 0;
     return run_field(fine_pass ? p.fm : p.coarse, a, p.cfg->precision, s, fold_wanted());
 }
 
@@ -1338,6 +1345,7 @@ int nerf_amd_set_tuning(int key, int value) {
     if (key == 0 && value >= 0 && value <= 115) { g_variant.store(value, std::memory_order_relaxed); return NERF_AMD_OK; }
     if (key == 1 && value >= 0 && value <= 1) { g_density_route.store(value, std::memory_order_relaxed); return NERF_AMD_OK; }
     if (key == 2 && value >= 0 && value <= 2) { g_fold.store(value, std::memory_order_relaxed); return NERF_AMD_OK; }
+    if (key == 3 && value >= 0 && value <= 1) { g_view_skip_off.store(value, std::memory_order_relaxed); return NERF_AMD_OK; }
     return fail(NERF_AMD_EINVAL, "unknown tuning key/value");
 }
 

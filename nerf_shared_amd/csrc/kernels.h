@@ -35,6 +35,9 @@ struct MlpArgs {
     int32_t S;                     // samples per ray (ray index = p / S)
     int32_t out_ch;
     float *out;                    // [P, out_ch]
+    int32_t view_skip;             // folded bf16 kernels (mlp_bf16_s16.hip view_branch_fold): 1 = a 16-point column tile whose sigmas are
+                                   // all <= 0 gets rgb = 0 without its colour branch being computed.  Only for a caller that reads
+                                   // rgb through weights that are exactly 0 there (capi.hip stage_field); 0 everywhere else
     unsigned *tile_ctr;            // mlp_bf16_s16p_kernel: {next ticket, workgroups done} of this launch (tile_counter_slot), or NULL:
                                    // tiles dealt blockIdx, blockIdx + gridDim, ... (the static deal)
     // training: every saved / gradient array below has pad_points(P) rows (the kernels store the rows of a

@@ -151,6 +151,88 @@ __device__ __forceinline__ void layer16(C &c, const bf16x8 *x1, const bf16x8 *x2
     });
 }
 
+// One column tile of the wave's two (the folded kernels' view branch where the other 16 points have no density, see
+// view_branch_fold): the same fragments in the same order, each feeding one MFMA; a column's sums do not depend on its
+// neighbour's, so its results are those of tile_pair / tile_single bit for bit.
+template <int F0, int T, int K1, int K2, int NB, int NFRAGS, class C>
+__device__ __forceinline__ void tile_pair_col(C &c, const bf16x8 *x1, const bf16x8 *x2, f32x4 (&acc)[2]) {
+    acc[0] = *reinterpret_cast<const f32x4 *>(c.bias_half + T * 16);
+    acc[1] = *reinterpret_cast<const f32x4 *>(c.bias_half + (T + 1) * 16);
+    static_for<K1 + K2>([&](auto k_) {
+        constexpr int k = k_, n = F0 + 2 * k;
+        const bf16x8 w0 = take<n, NB, NFRAGS>(c);
+        const bf16x8 w1 = take<n + 1, NB, NFRAGS>(c);
+        const bf16x8 x = k < K1 ? x1[k < K1 ? k : 0] : x2[k < K1 ? 0 : k - K1];
+        acc[0] = MFMA16(w0, x, acc[0]);
+        acc[1] = MFMA16(w1, x, acc[1]);
+        sched_step<C, 2, 2>();
+    });
+}
+template <int F0, int T, int K1, int NB, int NFRAGS, class C>
+__device__ __forceinline__ void tile_single_col(C &c, const bf16x8 *x1, f32x4 &acc) {
+    acc = *reinterpret_cast<const f32x4 *>(c.bias_half + T * 16);
+    static_for<K1>([&](auto k_) {
+        constexpr int k = k_;
+        const bf16x8 w0 = take<F0 + k, NB, NFRAGS>(c);
+        acc = MFMA16(w0, x1[k], acc);
+        sched_step<C, 1, 1>();
+    });
+}
+
+// The colour branch of the folded kernels (views_linears.0 over [W' | dirs], then the rgb head), per 16-point column tile
+// only where some point of the tile has density.  `live`: bit cc set = column tile cc is computed (wave-uniform; the caller
+// takes it from sigma, which the alpha tile in front of this branch has left in registers, or passes 3 = the plain path).
+//   3  both columns: layer16 + tile_single as always
+//   0  neither: the 8 (8 + KD) + 4 fragments pass unread -- their syncs, DMA issue sites and vmcnt counts stay where take<n>
+//      has them (pipeline.h skip_frags), so the waves of a workgroup may each go their own way -- and rgb is zero
+//   1, 2  one column: its activations are selected into one set of registers and every fragment feeds one MFMA instead of two;
+//      the other column's rgb is zero
+// Zero, not "whatever is there": the caller stores rgb for every point, and downstream 0 * rgb must be 0.
+// The three ways are a branch at the tile's tail (nothing but the output stores and the loop's back-edge follows), where it
+// does not split the scheduling region of the layers (pipeline.h issue_block).  h: the trunk's output (8 k-steps x 2 columns),
+// t: 8 fragments of scratch for the hidden view layer.
+template <class Lay, int KD, int NB, int NF, class C>
+__device__ __forceinline__ void view_branch_fold(C &c, const bf16x8 *h, const bf16x8 *Dv, bf16x8 *t, unsigned live, f32x4 (&rgb)[2]) {
+    const f32x4 zero = {0.0f, 0.0f, 0.0f, 0.0f};
+    if (live == 3u) {
+        layer16<Lay::F_VIEWS, Lay::T_VIEWS, 4, 8, KD, true, NB, NF>(c, h, Dv, t);      // views_linears.0 over [W' | dirs]: reads h8
+        tile_single<Lay::F_RGB, Lay::T_RGB, 4, NB, NF>(c, t, rgb);                     // rows 0..2
+    } else if (live == 0u) {
+        // the alpha tile's read-ahead has fragment reads of this branch in flight: they land before this wave reaches the
+        // syncs that let their ring slot be refilled
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        skip_frags<Lay::F_VIEWS, NF - Lay::F_VIEWS, NB, NF>(c);
+        rgb[0] = zero; rgb[1] = zero;
+    } else {
+        const bool second = live == 2u;
+        bf16x8 x[8], d[KD];
+#pragma unroll
+        for (int k = 0; k < 8; ++k) x[k] = second ? h[2 * k + 1] : h[2 * k];
+#pragma unroll
+        for (int k = 0; k < KD; ++k) d[k] = second ? Dv[2 * k + 1] : Dv[2 * k];
+        static_for<4>([&](auto p_) {
+            constexpr int p = p_;
+            f32x4 acc[2];
+            tile_pair_col<Lay::F_VIEWS + p * 2 * (8 + KD), Lay::T_VIEWS + 2 * p, 8, KD, NB, NF>(c, x, d, acc);
+            t[p] = pack_pair<true, !(C::OPT & 1)>(acc[0], acc[1]);
+        });
+        f32x4 r;
+        tile_single_col<Lay::F_RGB, Lay::T_RGB, 4, NB, NF>(c, t, r);
+        rgb[0] = second ? zero : r;
+        rgb[1] = second ? r : zero;
+    }
+}
+
+// Which of a wave's two column tiles view_branch_fold computes: bit cc is set unless every sigma of the tile's 16 points is
+// <= 0 (row 0 of the alpha tile: lane quarter 0, element 0) or lies past P.  A NaN compares false and keeps its tile.
+// skip == 0 (MlpArgs::view_skip): always 3.
+__device__ __forceinline__ unsigned live_columns(int skip, int q, const f32x4 (&alpha)[2], bool valid0, bool valid1) {
+    if (!skip) return 3u;
+    const unsigned long long l0 = __builtin_amdgcn_ballot_w64(q == 0 && valid0 && !(alpha[0][0] <= 0.0f));
+    const unsigned long long l1 = __builtin_amdgcn_ballot_w64(q == 0 && valid1 && !(alpha[1][0] <= 0.0f));
+    return (l0 ? 1u : 0u) | (l1 ? 2u : 0u);
+}
+
 // Positional encoding into FRAG_GEN16 layout (program.h: gen16_col).  h = sin/cos family,
 // b = frequency parity of this lane quarter.  th + tl = x / (2 pi) as an exact fp32 pair;
 // multiplying by 4 and v_fract are exact, v_sin_f32 takes revolutions.
@@ -447,8 +529,7 @@ __device__ __forceinline__ void mlp_bf16_s16_body(const MlpArgs &a) {
         f32x4 alpha[2], rgb[2];
         if constexpr (FOLD) {
             tile_single<Lay::F_ALPHA, Lay::T_ALPHA, 8, NB, NF>(c, B, alpha);               // row 0 = sigma
-            layer16<Lay::F_VIEWS, Lay::T_VIEWS, 4, 8, KD, true, NB, NF>(c, B, Dv, A);      // views_linears.0 over [W' | dirs]: reads h8
-            tile_single<Lay::F_RGB, Lay::T_RGB, 4, NB, NF>(c, A, rgb);                     // rows 0..2
+            view_branch_fold<Lay, KD, NB, NF>(c, B, Dv, A, live_columns(a.view_skip, q, alpha, valid[0], valid[1]), rgb);
         } else {
         layer16<Lay::F_FEAT, 128, 8, 8, 0, false, NB, NF>(c, B, B, A);     // feature (no activation)
         if constexpr (SAVE) save_frags<8, 256>(a.sv_feat, A, pidx, q);
@@ -766,8 +847,7 @@ __device__ __forceinline__ void mlp_bf16_s16p_body(const MlpArgs &a) {
         f32x4 alpha[2], rgb[2];
         if constexpr (FOLD) {
             tile_single<Lay::F_ALPHA, Lay::T_ALPHA, 8, NB, NF>(c, B, alpha);               // row 0 = sigma
-            layer16<Lay::F_VIEWS, Lay::T_VIEWS, 4, 8, KD, true, NB, NF>(c, B, Dv, A);      // views_linears.0 over [W' | dirs]: reads h8
-            tile_single<Lay::F_RGB, Lay::T_RGB, 4, NB, NF>(c, A, rgb);                     // rows 0..2
+            view_branch_fold<Lay, KD, NB, NF>(c, B, Dv, A, live_columns(a.view_skip, q, alpha, point_index(tile, 0) < P32, point_index(tile, 1) < P32), rgb);
         } else {
         layer16<Lay::F_FEAT, 128, 8, 8, 0, false, NB, NF>(c, B, B, A, hook_feat);   // feature (no activation) + this tile's view directions
         tile_single<Lay::F_ALPHA, Lay::T_ALPHA, 8, NB, NF>(c, B, alpha);   // row 0 = sigma
