@@ -443,6 +443,41 @@ int nerf_amd_rays_at_pixels_batch(int32_t H, int32_t W, const double *K4 /* HOST
                                   float *rays_d, void *stream);
 int nerf_amd_rays_at_pixels_batch_backward(int32_t H, int32_t W, const double *K4, const int32_t *pix, int64_t n, int32_t B,
                                            const float *g_rays_o, const float *g_rays_d, float *g_c2w, void *stream);
+/* Joint training of the field and the camera poses (BARF / iMAP-style mapping): a training batch mixes images, so every
+ * ray has its OWN pose.  nerf_amd_rays_at_pixels at n pixels where ray i takes pose p_i of the M in the table (1 <= M <=
+ * 1024; pose m at c2w + m * c2w_pose_stride floats, its row r a further r * c2w_row_stride floats on, as for
+ * nerf_amd_rays_at_pixels_batch); rays_o / rays_d [n,3], row i bit-equal to nerf_amd_rays_at_pixels with pose p_i at that
+ * pixel (the same device function).  0 <= n <= 2^31 - 1.
+ *   pose_index [n] int32 DEVICE:  p_i = pose_index[i], pix[i] = (x, y) in that image.
+ *   pose_index NULL:  pix[i] = (x, y) is a pixel of the M images stacked as one [M H, W] image (what nerf_amd_draw_pixels
+ *                     over the stacked bank draws): p_i = y / H, the row is y - p_i H.
+ * A p_i outside [0, M) never forms an address: that ray's o and d are NaN and it enters no gradient.
+ * _backward: g_rays_o / g_rays_d [n,3] (either may be NULL = zero) -> g_c2w [M,12] (overwritten).  ONE 1024-thread block
+ * per pose m runs the loop, butterfly and wave-order sum of nerf_amd_rays_at_pixels_backward's one-block path over ALL n
+ * rays, block-strided (so the 16384 limit of the batch form does not apply), and adds a ray's terms only when p_i == m --
+ * other rays are skipped, not added as zeros.  Order-fixed, no float atomics: equal inputs give equal bits; with every
+ * ray on pose m, row m is bit-equal to nerf_amd_rays_at_pixels_batch_backward at B = 1; a pose without rays gets +0.0. */
+int nerf_amd_rays_at_pixels_indexed(int32_t H, int32_t W, const double *K4 /* HOST */, const float *c2w, int64_t c2w_pose_stride,
+                                    int32_t c2w_row_stride, int32_t M, const int32_t *pix, const int32_t *pose_index,
+                                    int64_t n, float *rays_o, float *rays_d, void *stream);
+int nerf_amd_rays_at_pixels_indexed_backward(int32_t H, int32_t W, const double *K4, const int32_t *pix,
+                                             const int32_t *pose_index, int64_t n, int32_t M, const float *g_rays_o,
+                                             const float *g_rays_d, float *g_c2w, void *stream);
+/* se(3) twists: T_m = Exp(xi_m) X_m for M poses (1 <= M <= 1024), xi [M,6] = (omega[3], upsilon[3]), th = |omega|,
+ * K = [omega]x:
+ *   R = I + A K + B K^2     t = (I + B K + C K^2) upsilon     Exp(xi) = [R t; 0 0 0 1]
+ *   A = sin th / th         B = (1 - cos th) / th^2           C = (th - sin th) / th^3
+ * X at x + m * x_stride floats, x_stride = 0 (one [16] shared) or 16 ([M,16]); T [M,16].  One lane per pose; fp64 from
+ * the fp32 inputs, rounded once.  For th^2 < 1e-2 (th < 0.1) A, B, C and their derivatives A'/th, B'/th, C'/th are FIVE
+ * Taylor terms in th^2 (through th^8; truncation below 3e-18 relative); above it the closed forms, with 1 - cos th as
+ * 2 sin^2(th / 2), lose at most 2 eps64 / th^4 = 2e-10 relative (C'/th; C: 6 eps64 / th^2 < 1e-13) to cancellation, against
+ * an fp32 ulp of 6e-8.  xi_m = 0 gives T_m = X_m bit for bit.  Unlike nerf_amd_se3_transform's (w, v, theta), whose pose
+ * is bilinear in theta and (w, v) and has no derivative at zero, the twist's derivative at xi = 0 is the six generators
+ * applied to X: a correction can START at "none".
+ * _backward: g_T [M,16] -> g_xi [M,6] (overwritten), analytic in fp64, at xi = 0 too; X is a constant. */
+int nerf_amd_se3_exp_batch(const float *xi, const float *x, int32_t x_stride, int32_t M, float *T, void *stream);
+int nerf_amd_se3_exp_batch_backward(const float *xi, const float *x, int32_t x_stride, int32_t M, const float *g_T,
+                                    float *g_xi, void *stream);
 /* One loss per hypothesis: out[b] = mean((x[b] - y_b)^2), x [B,m]; y_b at y + b * y_stride floats, y_stride = 0 (one y [m]
  * shared) or m (y [B,m]).  One block per hypothesis: nerf_amd_img2mse's one-launch path, so 1 <= m <= 16384
  * (beyond it NERF_AMD_EINVAL, also at B = 1).  _backward: gx[b,i] = g[b] * 2 (x[b,i] - y_b[i]) / m, g [B] DEVICE, gx [B,m]. */

@@ -46,6 +46,8 @@ EXPORTS = (
     "nerf_amd_render_rays_culled_workspace", "nerf_amd_render_rays_culled",
     "nerf_amd_occupancy_cull_capped", "nerf_amd_occupancy_gather_rows", "nerf_amd_occupancy_ray_grads",
     "nerf_amd_occupancy_ray_bounds", "nerf_amd_occupancy_coarse_z",
+    "nerf_amd_rays_at_pixels_indexed", "nerf_amd_rays_at_pixels_indexed_backward", "nerf_amd_se3_exp_batch",
+    "nerf_amd_se3_exp_batch_backward",
 )
 OCC_OUTSIDE_LIVE, OCC_OUTSIDE_EMPTY = 0, 1
 
@@ -146,6 +148,12 @@ def _load():
                                                   c_int64, c_void_p, c_void_p, c_void_p]),
         "nerf_amd_rays_at_pixels_batch_backward": (c_int, [c_int32, c_int32, POINTER(c_double), c_void_p, c_int64, c_int32, c_void_p,
                                                            c_void_p, c_void_p, c_void_p]),
+        "nerf_amd_rays_at_pixels_indexed": (c_int, [c_int32, c_int32, POINTER(c_double), c_void_p, c_int64, c_int32, c_int32, c_void_p,
+                                                    c_void_p, c_int64, c_void_p, c_void_p, c_void_p]),
+        "nerf_amd_rays_at_pixels_indexed_backward": (c_int, [c_int32, c_int32, POINTER(c_double), c_void_p, c_void_p, c_int64, c_int32,
+                                                             c_void_p, c_void_p, c_void_p, c_void_p]),
+        "nerf_amd_se3_exp_batch": (c_int, [c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_void_p]),
+        "nerf_amd_se3_exp_batch_backward": (c_int, [c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_void_p, c_void_p]),
         "nerf_amd_img2mse_each": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_int32, c_void_p, c_void_p]),
         "nerf_amd_img2mse_each_backward": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_int32, c_void_p, c_void_p, c_void_p]),
         "nerf_amd_draw_pixels": (c_int, [c_int64, c_int32, c_uint32, c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_int64, c_int32,

@@ -1505,6 +1505,37 @@ int nerf_amd_rays_at_pixels_backward(int32_t H, int32_t W, const double *K4, con
                        "n > 16384 needs the partials buffer (256 * 12 floats)");
 }
 
+int nerf_amd_rays_at_pixels_indexed(int32_t H, int32_t W, const double *K4, const float *c2w, int64_t c2w_pose_stride,
+                                    int32_t c2w_row_stride, int32_t M, const int32_t *pix, const int32_t *pose_index, int64_t n,
+                                    float *rays_o, float *rays_d, void *stream) {
+    const bool ok = rays_ok(H, W, K4, pix, n) && n <= RAYS_INDEXED_MAX && c2w && c2w_pose_stride >= 0 && c2w_row_stride >= 4 &&
+                    (n == 0 || (rays_o && rays_d));
+    if (int rc = pose_refusal("rays_at_pixels_indexed", ok, M)) return rc;
+    return pose_result("rays_at_pixels_indexed", launch_rays_at_pixels_indexed(H, K4, c2w, c2w_pose_stride, c2w_row_stride, M, pix,
+                                                                               pose_index, n, rays_o, rays_d,
+                                                                               static_cast<hipStream_t>(stream)));
+}
+
+int nerf_amd_rays_at_pixels_indexed_backward(int32_t H, int32_t W, const double *K4, const int32_t *pix, const int32_t *pose_index,
+                                             int64_t n, int32_t M, const float *g_rays_o, const float *g_rays_d, float *g_c2w,
+                                             void *stream) {
+    if (int rc = pose_refusal("rays_at_pixels_indexed_backward", rays_ok(H, W, K4, pix, n) && n <= RAYS_INDEXED_MAX && g_c2w, M)) return rc;
+    return pose_result("rays_at_pixels_indexed_backward",
+                       launch_rays_at_pixels_indexed_bwd(H, K4, pix, pose_index, n, M, g_rays_o, g_rays_d, g_c2w,
+                                                         static_cast<hipStream_t>(stream)));
+}
+
+int nerf_amd_se3_exp_batch(const float *xi, const float *x, int32_t x_stride, int32_t M, float *T, void *stream) {
+    if (int rc = pose_refusal("se3_exp_batch", xi && x && (x_stride == 0 || x_stride == 16) && T, M)) return rc;
+    return pose_result("se3_exp_batch", launch_se3_exp(xi, x, x_stride, M, T, static_cast<hipStream_t>(stream)));
+}
+
+int nerf_amd_se3_exp_batch_backward(const float *xi, const float *x, int32_t x_stride, int32_t M, const float *g_T, float *g_xi,
+                                    void *stream) {
+    if (int rc = pose_refusal("se3_exp_batch_backward", xi && x && (x_stride == 0 || x_stride == 16) && g_T && g_xi, M)) return rc;
+    return pose_result("se3_exp_batch_backward", launch_se3_exp_bwd(xi, x, x_stride, M, g_T, g_xi, static_cast<hipStream_t>(stream)));
+}
+
 int nerf_amd_img2mse_each(const float *x, const float *y, int64_t y_stride, int64_t m, int32_t B, float *out, void *stream) {
     if (int rc = pose_refusal("img2mse_each", mse_ok(x, y, y_stride, m) && out, B)) return rc;
     return pose_result("img2mse_each", na::launch_img2mse(x, y, y_stride, m, B, out, nullptr, static_cast<hipStream_t>(stream)), ONE_BLOCK_M);

@@ -223,6 +223,19 @@ int launch_rays_at_pixels_bwd(const double *K4, const int32_t *pix, int64_t n, i
 int launch_img2mse(const float *x, const float *y, int64_t y_stride, int64_t n, int B, float *out, float *partials, hipStream_t s);
 int launch_img2mse_bwd(const float *x, const float *y, int64_t y_stride, int64_t n, int B, const float *g, float *gx, float *gy,
                        hipStream_t s);
+// joint training of field and poses: rays whose pose differs per ray (ray i takes pose p_i of M; one block per pose in the
+// backward, block-strided over all n rays, so no one-block limit -- any n < 2^31), and the se(3) twist T = Exp(xi) X, whose
+// coefficients come from SE3_SERIES_TERMS Taylor terms below |omega|^2 < SE3_SERIES_TH2 (render.hip).
+constexpr int64_t RAYS_INDEXED_MAX = 0x7fffffff;
+constexpr double SE3_SERIES_TH2 = 1e-2;
+constexpr int SE3_SERIES_TERMS = 5;
+int launch_rays_at_pixels_indexed(int H, const double *K4, const float *c2w, int64_t c2w_pose_stride, int c2w_row_stride, int M,
+                                  const int32_t *pix, const int32_t *pose_index, int64_t n, float *rays_o, float *rays_d,
+                                  hipStream_t s);
+int launch_rays_at_pixels_indexed_bwd(int H, const double *K4, const int32_t *pix, const int32_t *pose_index, int64_t n, int M,
+                                      const float *g_o, const float *g_d, float *g_c2w, hipStream_t s);
+int launch_se3_exp(const float *xi, const float *x, int x_stride, int M, float *T, hipStream_t s);
+int launch_se3_exp_bwd(const float *xi, const float *x, int x_stride, int M, const float *g_T, float *g_xi, hipStream_t s);
 // pixel selection for pose estimation (pixel_select.hip; demo_est_rel_pose.py:35-47, :75-79)
 int launch_draw_pixels(int64_t M, int n, uint32_t seed, int64_t *draw_count, const int32_t *region, int W, const float *image,
                        int64_t row_stride, int C, int32_t *pixels, float *target, hipStream_t s);

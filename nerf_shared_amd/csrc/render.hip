@@ -957,16 +957,37 @@ int launch_rays_at_pixels(const double *K4, const float *c2w, int64_t c2w_pose_s
 // The loop is grid-strided, so any grid covers any n: RAYS_AT_BWD_PER_BLOCK (kernels.h) only chooses how many blocks are
 // launched (reduce_blocks above: <= RAYS_AT_BWD_MAX_BLOCKS = the rows of `partials`) and need not be a multiple of the block size.
 constexpr int RAP_BLOCK = 1024;
-// Block `block` of `n_blocks` of one pose's gradient.
+// Which pose a ray of an INDEXED launch belongs to, and its pixel row there.  pose_index [n] names the pose; without it the
+// pixel is one of the M images stacked as one [M H, W] image (what a draw over the stacked bank produces): pose y / H, row
+// y - pose * H.  The result is only ever COMPARED or range-checked by the callers before it forms an address.
+struct PoseOfRay { int pose, row; };
+__device__ __forceinline__ PoseOfRay pose_of_ray(const int32_t *pix, const int32_t *pose_index, int H, int64_t idx) {
+    const int y = pix[2 * idx + 1];
+    if (pose_index) return {pose_index[idx], y};
+    const int p = y < 0 ? -1 : y / H;
+    return {p, y - p * H};
+}
+
+// Block `block` of `n_blocks` of one pose's gradient.  INDEXED: only the rays of pose `mine` are added (the others are
+// skipped, not added as zeros), so with every ray on `mine` the sums are those of the plain form bit for bit.
+template <bool INDEXED>
 __device__ __forceinline__ void rays_at_pixels_bwd_block(PixCam k, const int32_t *pix, int64_t n, const float *g_o, const float *g_d,
                                                          float *g_c2w, float *partials, int block, int n_blocks,
-                                                         float (*part)[12] /* [RAP_BLOCK / 64][12] LDS */) {
+                                                         float (*part)[12] /* [RAP_BLOCK / 64][12] LDS */,
+                                                         const int32_t *pose_index = nullptr, int H = 0, int mine = 0) {
     float acc[12];
 #pragma unroll
     for (int i = 0; i < 12; ++i) acc[i] = 0.f;
     const int64_t stride = (int64_t)n_blocks * RAP_BLOCK;
     for (int64_t idx = (int64_t)block * RAP_BLOCK + threadIdx.x; idx < n; idx += stride) {
-        const float i = (float)pix[2 * idx], j = (float)pix[2 * idx + 1];
+        float i = (float)pix[2 * idx], j;
+        if (INDEXED) {
+            const PoseOfRay pr = pose_of_ray(pix, pose_index, H, idx);
+            if (pr.pose != mine) continue;
+            j = (float)pr.row;
+        } else {
+            j = (float)pix[2 * idx + 1];
+        }
         const float dir[3] = {(i - k.cx) / k.fx, -(j - k.cy) / k.fy, -1.0f};
 #pragma unroll
         for (int r = 0; r < 3; ++r) {
@@ -997,8 +1018,8 @@ __global__ __launch_bounds__(RAP_BLOCK) void rays_at_pixels_bwd_kernel(PixCam k,
                                                                        const float *g_d, float *g_c2w, float *partials) {
     __shared__ float part[RAP_BLOCK / 64][12];
     const int64_t b = blockIdx.y;
-    rays_at_pixels_bwd_block(k, pix, n, g_o ? g_o + b * n * 3 : nullptr, g_d ? g_d + b * n * 3 : nullptr, g_c2w + b * 12, partials,
-                             (int)blockIdx.x, (int)gridDim.x, part);
+    rays_at_pixels_bwd_block<false>(k, pix, n, g_o ? g_o + b * n * 3 : nullptr, g_d ? g_d + b * n * 3 : nullptr, g_c2w + b * 12,
+                                    partials, (int)blockIdx.x, (int)gridDim.x, part);
 }
 
 __global__ __launch_bounds__(64) void rays_at_pixels_bwd_finish_kernel(const float *partials, int n_parts, float *g_c2w) {
@@ -1018,6 +1039,57 @@ int launch_rays_at_pixels_bwd(const double *K4, const int32_t *pix, int64_t n, i
     hipLaunchKernelGGL(rays_at_pixels_bwd_kernel, dim3((unsigned)blocks, (unsigned)B), dim3(RAP_BLOCK), 0, s, k, pix, n, g_o, g_d, g_c2w,
                        partials);
     if (blocks > 1) hipLaunchKernelGGL(rays_at_pixels_bwd_finish_kernel, dim3(1), dim3(64), 0, s, partials, blocks, g_c2w);
+    return hipGetLastError() == hipSuccess ? NERF_AMD_OK : NERF_AMD_EHIP;
+}
+
+// ---- rays whose pose differs per ray (joint training of the field and the camera poses: a batch mixes images) ---------
+// One thread per ray: ray i takes pose p_i of the M in the table (pose_of_ray above) and is ray_at_pixel with that pose at
+// its pixel, so it equals the single-pose launch bit for bit.  A p_i outside [0, M) never forms an address: the ray is NaN.
+__global__ __launch_bounds__(256) void rays_at_pixels_indexed_kernel(PixCam k, const float *c2w, int64_t pose_stride, int stride, int M,
+                                                                     int H, const int32_t *pix, const int32_t *pose_index, int64_t n,
+                                                                     float *rays_o, float *rays_d) {
+    const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx >= n) return;
+    const PoseOfRay pr = pose_of_ray(pix, pose_index, H, idx);
+    float *o = rays_o + 3 * idx, *d = rays_d + 3 * idx;
+    if (pr.pose < 0 || pr.pose >= M) {
+        const float nan = __builtin_nanf("");
+        o[0] = o[1] = o[2] = d[0] = d[1] = d[2] = nan;
+        return;
+    }
+    const int32_t xy[2] = {pix[2 * idx], pr.row};
+    ray_at_pixel(k, c2w + pr.pose * pose_stride, stride, xy, 0, o, d);
+}
+
+int launch_rays_at_pixels_indexed(int H, const double *K4, const float *c2w, int64_t c2w_pose_stride, int c2w_row_stride, int M,
+                                  const int32_t *pix, const int32_t *pose_index, int64_t n, float *rays_o, float *rays_d,
+                                  hipStream_t s) {
+    if (M < 1 || M > POSE_BATCH_MAX || H < 1 || n > RAYS_INDEXED_MAX) return NERF_AMD_EINVAL;
+    if (n <= 0) return NERF_AMD_OK;
+    const PixCam k = {(float)K4[0], (float)K4[1], (float)K4[2], (float)K4[3]};
+    hipLaunchKernelGGL(rays_at_pixels_indexed_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, k, c2w, c2w_pose_stride,
+                       c2w_row_stride, M, H, pix, pose_index, n, rays_o, rays_d);
+    return hipGetLastError() == hipSuccess ? NERF_AMD_OK : NERF_AMD_EHIP;
+}
+
+// grid (M): block m is pose m's gradient, the one-block path of rays_at_pixels_bwd_block over ALL n rays with the rays of
+// other poses skipped.  Every block reads every ray's index (M n loads of L2-resident data; M <= 1024): no sort, no atomics,
+// a fixed order.  A pose without rays ends with +0.0 in all 12 entries.
+__global__ __launch_bounds__(RAP_BLOCK) void rays_at_pixels_indexed_bwd_kernel(PixCam k, int H, const int32_t *pix,
+                                                                               const int32_t *pose_index, int64_t n, const float *g_o,
+                                                                               const float *g_d, float *g_c2w) {
+    __shared__ float part[RAP_BLOCK / 64][12];
+    const int m = blockIdx.x;
+    rays_at_pixels_bwd_block<true>(k, pix, n, g_o, g_d, g_c2w + (int64_t)m * 12, nullptr, 0, 1, part, pose_index, H, m);
+}
+
+int launch_rays_at_pixels_indexed_bwd(int H, const double *K4, const int32_t *pix, const int32_t *pose_index, int64_t n, int M,
+                                      const float *g_o, const float *g_d, float *g_c2w, hipStream_t s) {
+    if (M < 1 || M > POSE_BATCH_MAX || H < 1 || n > RAYS_INDEXED_MAX) return NERF_AMD_EINVAL;
+    if (n <= 0) return hipMemsetAsync(g_c2w, 0, (size_t)M * 12 * sizeof(float), s) == hipSuccess ? NERF_AMD_OK : NERF_AMD_EHIP;
+    const PixCam k = {(float)K4[0], (float)K4[1], (float)K4[2], (float)K4[3]};
+    hipLaunchKernelGGL(rays_at_pixels_indexed_bwd_kernel, dim3((unsigned)M), dim3(RAP_BLOCK), 0, s, k, H, pix, pose_index, n, g_o, g_d,
+                       g_c2w);
     return hipGetLastError() == hipSuccess ? NERF_AMD_OK : NERF_AMD_EHIP;
 }
 
@@ -1139,6 +1211,138 @@ int launch_se3_transform_bwd(const float *w, const float *v, const float *theta,
     if (B < 1 || B > POSE_BATCH_MAX || (x_stride != 0 && x_stride != 16)) return NERF_AMD_EINVAL;
     hipLaunchKernelGGL(se3_transform_bwd_kernel, dim3((unsigned)((B + 63) / 64)), dim3(64), 0, s, w, v, theta, x, x_stride, B, g_T, g_w,
                        g_v, g_theta);
+    return hipGetLastError() == hipSuccess ? NERF_AMD_OK : NERF_AMD_EHIP;
+}
+
+// ---------------------------------------------------------------------------
+// se(3) twists (joint training of poses): T = Exp(xi) X, xi = (omega, upsilon), th = |omega|, K = [omega]x,
+//   R = I + A K + B K^2,   t = (I + B K + C K^2) upsilon,   A = sin th / th, B = (1 - cos th) / th^2, C = (th - sin th) / th^3.
+// Unlike exp_i above (bilinear in theta and (w, v)) the map is smooth with a full-rank derivative at xi = 0: the six
+// generators applied to X.  One lane per pose, fp64 from the fp32 inputs, rounded once.
+// Below th^2 < SE3_SERIES_TH2 (th < 0.1) A, B, C and A'/th, B'/th, C'/th come from SE3_SERIES_TERMS = 5 Taylor terms (through
+// th^8; the next term is below 3e-18 of the first).  Above it the closed forms lose at most 6 eps64 / th^2 < 1e-13 (C) and
+// 2 eps64 / th^4 (C'/th, relative: 2e-10) to cancellation -- hundreds of times below an fp32 ulp (6e-8).
+// ---------------------------------------------------------------------------
+struct Twist {
+    double w[3], u[3], A, B, C, a1, b1, c1;          // a1 = A'/th = C - B, b1 = B'/th = (A - 2B)/th^2, c1 = C'/th = (B - 3C)/th^2
+    double K[3][3], K2[3][3];
+};
+
+__device__ __forceinline__ Twist twist_load(const float *xi) {
+    Twist e;
+    for (int i = 0; i < 3; ++i) { e.w[i] = xi[i]; e.u[i] = xi[3 + i]; }
+    const double t2 = e.w[0] * e.w[0] + e.w[1] * e.w[1] + e.w[2] * e.w[2];
+    static_assert(SE3_SERIES_TERMS == 5, "the series below are written out to five terms");
+    if (t2 < SE3_SERIES_TH2) {
+        e.A = 1.0 - t2 * (1.0 / 6 - t2 * (1.0 / 120 - t2 * (1.0 / 5040 - t2 * (1.0 / 362880))));
+        e.B = 1.0 / 2 - t2 * (1.0 / 24 - t2 * (1.0 / 720 - t2 * (1.0 / 40320 - t2 * (1.0 / 3628800))));
+        e.C = 1.0 / 6 - t2 * (1.0 / 120 - t2 * (1.0 / 5040 - t2 * (1.0 / 362880 - t2 * (1.0 / 39916800))));
+        e.b1 = -(1.0 / 12 - t2 * (1.0 / 180 - t2 * (1.0 / 6720 - t2 * (1.0 / 453600 - t2 * (1.0 / 47900160)))));
+        e.c1 = -(1.0 / 60 - t2 * (1.0 / 1260 - t2 * (1.0 / 60480 - t2 * (1.0 / 4989600 - t2 * (1.0 / 622702080)))));
+    } else {
+        const double th = sqrt(t2), h = sin(0.5 * th);
+        e.A = sin(th) / th;
+        e.B = 2.0 * h * h / t2;                       // 1 - cos th = 2 sin^2(th / 2): no cancellation
+        e.C = (th - sin(th)) / (t2 * th);
+        e.b1 = (e.A - 2.0 * e.B) / t2;
+        e.c1 = (e.B - 3.0 * e.C) / t2;
+    }
+    e.a1 = e.C - e.B;
+    const double K[3][3] = {{0.0, -e.w[2], e.w[1]}, {e.w[2], 0.0, -e.w[0]}, {-e.w[1], e.w[0], 0.0}};
+    for (int i = 0; i < 3; ++i)
+        for (int j = 0; j < 3; ++j) {
+            e.K[i][j] = K[i][j];
+            e.K2[i][j] = K[i][0] * K[0][j] + K[i][1] * K[1][j] + K[i][2] * K[2][j];
+        }
+    return e;
+}
+
+__device__ __forceinline__ void twist_forward(const float *xi, const float *x, float *T) {
+    bool zero = true;
+    for (int i = 0; i < 6; ++i) zero = zero && xi[i] == 0.0f;
+    if (zero) {                                       // Exp(0) = I: X itself, bit for bit (an fp64 sum would turn -0.0 into +0.0)
+        for (int i = 0; i < 16; ++i) T[i] = x[i];
+        return;
+    }
+    const Twist e = twist_load(xi);
+    double E[3][4];
+    for (int i = 0; i < 3; ++i) {
+        double t = 0.0;
+        for (int j = 0; j < 3; ++j) {
+            const double id = i == j ? 1.0 : 0.0;
+            E[i][j] = id + e.A * e.K[i][j] + e.B * e.K2[i][j];
+            t += (id + e.B * e.K[i][j] + e.C * e.K2[i][j]) * e.u[j];
+        }
+        E[i][3] = t;
+    }
+    for (int j = 0; j < 4; ++j) {
+        for (int i = 0; i < 3; ++i) {
+            double t = 0.0;
+            for (int m = 0; m < 3; ++m) t += E[i][m] * (double)x[4 * m + j];
+            T[4 * i + j] = (float)(t + E[i][3] * (double)x[12 + j]);
+        }
+        T[12 + j] = x[12 + j];                        // the last row of Exp(xi) is (0, 0, 0, 1)
+    }
+}
+
+// M poses, one lane each: xi [M, 6], x at m * x_stride (0 = shared), T [M, 16].
+__global__ __launch_bounds__(64) void se3_exp_kernel(const float *xi, const float *x, int x_stride, int M, float *T) {
+    const int m = blockIdx.x * 64 + threadIdx.x;
+    if (m >= M) return;
+    twist_forward(xi + 6 * m, x + m * x_stride, T + 16 * m);
+}
+
+// dL/dxi from g_T: g_E = g_T x^T (rows 0..2), G_R = g_E[:, :3], g_t = g_E[:, 3], G_V = g_t upsilon^T.  With <G, K> linear and
+// <G, K^2> = omega^T G omega - th^2 tr G:
+//   g_upsilon = (I + B K + C K^2)^T g_t
+//   G1 = A G_R + B G_V,  G2 = B G_R + C G_V,  s = a1 <G_R, K> + b1 (<G_R, K^2> + <G_V, K>) + c1 <G_V, K^2>
+//   g_omega   = s omega + vee(G1 - G1^T) + (G2 + G2^T) omega - 2 tr(G2) omega
+// At xi = 0 (A = 1, G_V = 0): g_omega = vee(G_R - G_R^T), g_upsilon = g_t -- the six generators applied to X, none of them zero.
+__device__ __forceinline__ void twist_backward(const float *xi, const float *x, const float *g_T, float *g_xi) {
+    const Twist e = twist_load(xi);
+    double GR[3][3], gt[3], GV[3][3];
+    for (int i = 0; i < 3; ++i)
+        for (int j = 0; j < 4; ++j) {
+            double t = 0.0;
+            for (int m = 0; m < 4; ++m) t += (double)g_T[4 * i + m] * (double)x[4 * j + m];
+            if (j < 3) GR[i][j] = t; else gt[i] = t;
+        }
+    double gu[3] = {0.0, 0.0, 0.0}, s = 0.0, G1[3][3], G2[3][3];
+    for (int i = 0; i < 3; ++i)
+        for (int j = 0; j < 3; ++j) {
+            const double id = i == j ? 1.0 : 0.0;
+            GV[i][j] = gt[i] * e.u[j];
+            gu[j] += (id + e.B * e.K[i][j] + e.C * e.K2[i][j]) * gt[i];
+            s += e.a1 * GR[i][j] * e.K[i][j] + e.b1 * (GR[i][j] * e.K2[i][j] + GV[i][j] * e.K[i][j]) + e.c1 * GV[i][j] * e.K2[i][j];
+            G1[i][j] = e.A * GR[i][j] + e.B * GV[i][j];
+            G2[i][j] = e.B * GR[i][j] + e.C * GV[i][j];
+        }
+    const double tr2 = G2[0][0] + G2[1][1] + G2[2][2];
+    const double vee[3] = {G1[2][1] - G1[1][2], G1[0][2] - G1[2][0], G1[1][0] - G1[0][1]};
+    for (int k = 0; k < 3; ++k) {
+        double q = 0.0;
+        for (int j = 0; j < 3; ++j) q += (G2[k][j] + G2[j][k]) * e.w[j];
+        g_xi[k] = (float)(s * e.w[k] + vee[k] + q - 2.0 * tr2 * e.w[k]);
+        g_xi[3 + k] = (float)gu[k];
+    }
+}
+
+__global__ __launch_bounds__(64) void se3_exp_bwd_kernel(const float *xi, const float *x, int x_stride, int M, const float *g_T,
+                                                         float *g_xi) {
+    const int m = blockIdx.x * 64 + threadIdx.x;
+    if (m >= M) return;
+    twist_backward(xi + 6 * m, x + m * x_stride, g_T + 16 * m, g_xi + 6 * m);
+}
+
+int launch_se3_exp(const float *xi, const float *x, int x_stride, int M, float *T, hipStream_t s) {
+    if (M < 1 || M > POSE_BATCH_MAX || (x_stride != 0 && x_stride != 16)) return NERF_AMD_EINVAL;
+    hipLaunchKernelGGL(se3_exp_kernel, dim3((unsigned)((M + 63) / 64)), dim3(64), 0, s, xi, x, x_stride, M, T);
+    return hipGetLastError() == hipSuccess ? NERF_AMD_OK : NERF_AMD_EHIP;
+}
+
+int launch_se3_exp_bwd(const float *xi, const float *x, int x_stride, int M, const float *g_T, float *g_xi, hipStream_t s) {
+    if (M < 1 || M > POSE_BATCH_MAX || (x_stride != 0 && x_stride != 16)) return NERF_AMD_EINVAL;
+    hipLaunchKernelGGL(se3_exp_bwd_kernel, dim3((unsigned)((M + 63) / 64)), dim3(64), 0, s, xi, x, x_stride, M, g_T, g_xi);
     return hipGetLastError() == hipSuccess ? NERF_AMD_OK : NERF_AMD_EHIP;
 }
 

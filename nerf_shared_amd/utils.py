@@ -284,6 +284,92 @@ def get_rays_at(H, W, K, c2w, pixels):
     return _RaysAtPixelsFn.apply(pose, pix, int(H), int(W), K4)
 
 
+class _RaysIndexedFn(torch.autograd.Function):
+    """get_rays_indexed with a HIP backward with respect to the pose table (one block per pose, fixed order); pose_index None
+    is the stacked-row mode of nerf_amd_rays_at_pixels_indexed."""
+
+    @staticmethod
+    def forward(ctx, c2w, pix, pose_index, H, W, K4):
+        dev, n, M = c2w.device, pix.shape[0], c2w.shape[0]
+        o, d = torch.empty(n, 3, device=dev, dtype=torch.float32), torch.empty(n, 3, device=dev, dtype=torch.float32)
+        k4 = (ctypes.c_double * 4)(*K4)
+        with torch.cuda.device(dev):
+            _lib.check(lib.nerf_amd_rays_at_pixels_indexed(H, W, k4, c2w.data_ptr(), c2w.stride(0), c2w.stride(1), M, pix.data_ptr(),
+                                                           _lib.ptr(pose_index), n, o.data_ptr(), d.data_ptr(), _lib.stream_of(dev)),
+                       "nerf_amd_rays_at_pixels_indexed")
+        ctx.meta = (H, W, K4, tuple(c2w.shape))
+        ctx.pix, ctx.pose_index = pix, pose_index
+        return o, d
+
+    @staticmethod
+    def backward(ctx, g_o, g_d):
+        H, W, K4, shape = ctx.meta
+        pix, pose_index = ctx.pix, ctx.pose_index
+        dev = pix.device
+        g_o = None if g_o is None else g_o.contiguous().float()
+        g_d = None if g_d is None else g_d.contiguous().float()
+        k4 = (ctypes.c_double * 4)(*K4)
+        g = torch.empty(shape[0], 3, 4, device=dev, dtype=torch.float32)
+        with torch.cuda.device(dev):
+            _lib.check(lib.nerf_amd_rays_at_pixels_indexed_backward(H, W, k4, pix.data_ptr(), _lib.ptr(pose_index), pix.shape[0], shape[0],
+                                                                    _lib.ptr(g_o), _lib.ptr(g_d), g.data_ptr(), _lib.stream_of(dev)),
+                       "nerf_amd_rays_at_pixels_indexed_backward")
+        if shape[1] > 3:                           # row 3 of a [4, 4] pose gets no gradient
+            rows = g
+            g = torch.zeros(shape, device=dev, dtype=torch.float32)
+            g[:, :3] = rows
+        return g, None, None, None, None, None
+
+
+def _host_pose_index(pose_index, n, M):
+    """Host pose indices (list, array, CPU tensor) as a checked int32 CPU tensor [n]: they select rows of the pose table."""
+    host = torch.as_tensor(np.asarray(pose_index) if not isinstance(pose_index, torch.Tensor) else pose_index)
+    if host.dim() != 1 or host.shape[0] != n or host.is_floating_point():
+        raise _lib.NerfAmdError("pose_index must be %d integers (one per pixel), got %s %s" % (n, host.dtype, tuple(host.shape)))
+    if host.numel() > 0 and (int(host.min()) < 0 or int(host.max()) >= M):
+        raise _lib.NerfAmdError("pose_index outside [0, %d): the table holds %d poses" % (M, M))
+    return host.to(torch.int32).contiguous()
+
+
+def get_rays_indexed(H, W, K, c2w, pixels, pose_index=None):
+    """rays_o, rays_d [n, 3] of n pixels where ray i has its OWN pose out of a table: what a training batch that mixes
+    images needs when the poses are learned.  c2w is a DEVICE tensor [M, 3, 4] or [M, 4, 4] (1 <= M <= 1024), read on the
+    device; row i is get_rays_at(H, W, K, c2w[p_i], pixel_i) bit for bit.
+
+      pose_index [n] integers:  p_i = pose_index[i] and pixels [n, 2] = (x, y) in that image;
+      pose_index None:          pixels [n, 2] = (x, y) address the M images stacked as one [M H, W] image (what
+                                ImageBankSampler.draw() returns): p_i = y // H, the row is y - p_i H.
+
+    Differentiable with respect to c2w: the backward is one block per pose, in a fixed order (equal inputs, equal bits), any
+    n.  Same stride, dtype and device rules as get_rays_at: host pixels / indices outside the image / [0, M) raise
+    NerfAmdError; DEVICE tensors are trusted (checking would synchronise) -- and harmless: a pose index outside [0, M)
+    never forms an address, that ray is NaN and enters no gradient.  No host copy, no synchronisation: capturable."""
+    if not isinstance(c2w, torch.Tensor) or c2w.dim() != 3 or c2w.shape[1] not in (3, 4) or c2w.shape[2] != 4 \
+            or not 1 <= c2w.shape[0] <= POSE_BATCH_MAX:
+        raise _lib.NerfAmdError("a pose table must be a tensor [M, 3, 4] or [M, 4, 4] with 1 <= M <= %d, got %s"
+                                % (POSE_BATCH_MAX, tuple(getattr(c2w, "shape", ())) or type(c2w).__name__))
+    H, W, M = int(H), int(W), c2w.shape[0]
+    cpu = torch.device("cpu")
+    if not (isinstance(pixels, torch.Tensor) and pixels.is_cuda):              # host inputs are checked before anything else
+        pixels = _device_pixels(pixels, H if pose_index is not None else M * H, W, cpu)
+    if pose_index is not None and not (isinstance(pose_index, torch.Tensor) and pose_index.is_cuda):
+        pose_index = _host_pose_index(pose_index, pixels.shape[0], M)
+    if not c2w.is_cuda:
+        raise _lib.NerfAmdError("get_rays_indexed reads the poses on the device: c2w must be a ROCm tensor")
+    usable = c2w.dtype == torch.float32 and c2w.stride(2) == 1 and c2w.stride(1) >= 4 and c2w.stride(0) >= 0
+    pose = c2w if usable else c2w.float().contiguous()
+    pix = _device_pixels(pixels, H, W, pose.device) if pixels.is_cuda else pixels.to(pose.device)
+    if pose_index is not None:
+        if pose_index.dim() != 1 or pose_index.shape[0] != pix.shape[0] or pose_index.is_floating_point():
+            raise _lib.NerfAmdError("pose_index must be %d integers (one per pixel), got %s %s"
+                                    % (pix.shape[0], pose_index.dtype, tuple(pose_index.shape)))
+        pose_index = pose_index.to(device=pose.device, dtype=torch.int32).contiguous()
+    K4 = (float(K[0][0]), float(K[1][1]), float(K[0][2]), float(K[1][2]))
+    if not (pose.requires_grad and torch.is_grad_enabled()):
+        pose = pose.detach()
+    return _RaysIndexedFn.apply(pose, pix, pose_index, H, W, K4)
+
+
 class _Se3Fn(torch.autograd.Function):
     """T[b] = exp_i(w[b], v[b], theta[b]) x_b (nerf_amd_se3_transform_batch): one launch forward, one backward; x is a constant.
     w, v [3] and theta [] are B = 1 of w, v [B, 3] and theta [B] (contiguous): T and the gradients have the caller's shapes."""
@@ -380,6 +466,103 @@ class CameraTransfBatch(torch.nn.Module):
         with torch.no_grad():
             m.w.copy_(self.w[b]); m.v.copy_(self.v[b]); m.theta.copy_(self.theta[b])
         return m
+
+
+class _Se3ExpFn(torch.autograd.Function):
+    """T[m] = Exp(xi[m]) x_m (nerf_amd_se3_exp_batch): one launch forward, one backward; x is a constant."""
+
+    @staticmethod
+    def forward(ctx, xi, x):
+        M = xi.shape[0]
+        T = torch.empty(M, 4, 4, device=x.device, dtype=torch.float32)
+        ctx.x_stride = 16 if x.dim() == 3 else 0
+        with torch.cuda.device(x.device):
+            _lib.check(lib.nerf_amd_se3_exp_batch(xi.data_ptr(), x.data_ptr(), ctx.x_stride, M, T.data_ptr(), _lib.stream_of(x.device)),
+                       "nerf_amd_se3_exp_batch")
+        ctx.save_for_backward(xi, x)
+        return T
+
+    @staticmethod
+    def backward(ctx, g_T):
+        xi, x = ctx.saved_tensors
+        g = torch.empty_like(xi)
+        g_T = g_T.contiguous().float()
+        with torch.cuda.device(x.device):
+            _lib.check(lib.nerf_amd_se3_exp_batch_backward(xi.data_ptr(), x.data_ptr(), ctx.x_stride, xi.shape[0], g_T.data_ptr(),
+                                                           g.data_ptr(), _lib.stream_of(x.device)), "nerf_amd_se3_exp_batch_backward")
+        return g, None
+
+
+def _se3_exp(xi, x, me):
+    """Exp(xi) @ x for xi [M, 6] and x [4, 4] or [M, 4, 4]: the shape, device and dtype refusals, then the one Function."""
+    M = xi.shape[0]
+    if tuple(x.shape) not in ((4, 4), (M, 4, 4)):
+        raise _lib.NerfAmdError("%s(%d) takes a [4, 4] or [%d, 4, 4] pose, got %s" % (me, M, M, tuple(x.shape)))
+    _lib.require_device(x, "x")
+    _lib.require_device(xi, "%s's parameter" % me)
+    if xi.dtype != torch.float32 or xi.device != x.device:
+        raise _lib.NerfAmdError("%s's parameter must be fp32 on the pose's device (%s)" % (me, x.device))
+    return _Se3ExpFn.apply(xi.contiguous(), x.detach().float().contiguous())
+
+
+class SE3Twist(torch.nn.Module):
+    """n_poses rigid corrections as se(3) twists: the parameter is xi [M, 6] = (omega, upsilon) per pose, EXACTLY ZERO at
+    construction, and forward(x) = Exp(xi) @ x (include/nerf_amd.h, nerf_amd_se3_exp_batch) for one pose [4, 4] shared by all
+    or [M, 4, 4]; returns [M, 4, 4].  One launch each way, one lane per pose, fp64 inside; x is a constant.
+
+    Why not CameraTransfBatch: the demo's (w, v, theta) pose is bilinear in theta and (w, v), so at zero every derivative
+    vanishes and at its normal(0, 1e-6) start every derivative is a millionth of a gradient -- tolerable for one pose and
+    300 steps, wrong for hundreds of poses trained beside a field.  The twist's derivative at xi = 0 is the six generators
+    applied to x, so a correction can start at "none": forward at xi = 0 returns x bit for bit."""
+
+    def __init__(self, n_poses):
+        super().__init__()
+        M = int(n_poses)
+        if not 1 <= M <= POSE_BATCH_MAX:
+            raise _lib.NerfAmdError("SE3Twist holds 1..%d poses, got %d" % (POSE_BATCH_MAX, M))
+        self.xi = torch.nn.Parameter(torch.zeros(M, 6))
+
+    @property
+    def n_poses(self):
+        return self.xi.shape[0]
+
+    def forward(self, x):
+        return _se3_exp(self.xi, x, "SE3Twist")
+
+
+class LearnedPoses(torch.nn.Module):
+    """Camera poses that are trained beside the field: the given poses [M, 4, 4] (or [M, 3, 4]) as a buffer and an SE3Twist
+    `twist`; forward() returns the current poses Exp(xi_m) @ pose_m, [M, 4, 4].  A fresh module returns the given poses bit
+    for bit.  Rows listed in `frozen` always do, and their xi.grad is exactly zero (so Adam leaves them at zero): a
+    reconstruction is only defined up to a rigid motion of everything, and freezing one or two views fixes that gauge.
+    state_dict: poses, twist.xi."""
+
+    def __init__(self, poses, frozen=()):
+        super().__init__()
+        poses = torch.as_tensor(np.asarray(poses) if not isinstance(poses, torch.Tensor) else poses).detach().float()
+        if poses.dim() != 3 or tuple(poses.shape[1:]) not in ((3, 4), (4, 4)) or not 1 <= poses.shape[0] <= POSE_BATCH_MAX:
+            raise _lib.NerfAmdError("LearnedPoses takes poses [M, 4, 4] or [M, 3, 4] with 1 <= M <= %d, got %s"
+                                    % (POSE_BATCH_MAX, tuple(poses.shape)))
+        M = poses.shape[0]
+        if poses.shape[1] == 3:
+            poses = torch.cat([poses, poses.new_tensor([0., 0., 0., 1.]).expand(M, 1, 4)], 1)
+        frozen = sorted({int(i) for i in frozen})
+        if any(not 0 <= i < M for i in frozen):
+            raise _lib.NerfAmdError("frozen views %s are not all in [0, %d)" % (frozen, M))
+        self.frozen = tuple(frozen)
+        self.register_buffer("poses", poses.contiguous().clone())
+        free = torch.ones(M, 1)
+        free[list(frozen)] = 0.0
+        self.register_buffer("free", free, persistent=False)       # construction-time configuration, not state
+        self.twist = SE3Twist(M)
+
+    @property
+    def n_poses(self):
+        return self.poses.shape[0]
+
+    def forward(self):
+        xi = self.twist.xi * self.free if self.frozen else self.twist.xi      # a frozen row: xi 0 in, gradient times 0 out
+        return _se3_exp(xi, self.poses, "LearnedPoses")
 
 
 # ---------------------------------------------------------------- which pixels a pose-estimation step looks at
@@ -545,6 +728,39 @@ class PixelSampler:
     def reset(self, count=0):
         """The next draw is draw `count` (a device write, stream-ordered; no synchronisation)."""
         self.draw_count.fill_(int(count))
+
+
+class ImageBankSampler:
+    """Training batches drawn from the images themselves: PixelSampler's 'random' draw over a bank of M images [M, H, W, 3|4]
+    viewed as ONE [M H, W, C] image -- the same keyed draw, no new RNG, and no copy where the layout allows (a contiguous
+    fp32 device bank is used in place).  draw() -> (pixels [n_rays, 2] int32, target [n_rays, 3] fp32): n_rays distinct
+    pixels of the whole bank, (x, y) with y a row of the STACKED image, which is what get_rays_indexed(..., pose_index=None)
+    takes: image y // H, row y % H.  The bank costs 12 B per pixel (fp32 RGB) where pre-computed rays cost 72 B (origin,
+    direction, colour), and the rays follow the poses as they are learned.  M, H, W, n_rays, draw_count, reset(count),
+    pixels and target as PixelSampler has them.  M H W <= 2^31 - 1."""
+
+    def __init__(self, images, n_rays, seed=0, device=None):
+        if not isinstance(images, torch.Tensor):
+            images = np.asarray(images)
+        if images.ndim != 4 or images.shape[3] not in (3, 4) or min(images.shape[:3]) < 1:
+            raise _lib.NerfAmdError("the image bank must be [M, H, W, 3] or [M, H, W, 4], got %s" % (tuple(images.shape),))
+        M, H, W, C = (int(s) for s in images.shape)
+        if M * H * W > 0x7fffffff:
+            raise _lib.NerfAmdError("the bank holds %d x %d x %d = %d pixels; one draw addresses at most 2^31 - 1" % (M, H, W, M * H * W))
+        self.M, self.H, self.W = M, H, W
+        self._sampler = PixelSampler(images.reshape(M * H, W, C), n_rays, strategy="random", seed=seed, device=device)
+        self.n_rays, self.seed = self._sampler.n_rays, self._sampler.seed
+
+    pixels = property(lambda self: self._sampler.pixels)
+    target = property(lambda self: self._sampler.target)
+    draw_count = property(lambda self: self._sampler.draw_count)
+    image = property(lambda self: self._sampler.image)
+
+    def draw(self):
+        return self._sampler.draw()
+
+    def reset(self, count=0):
+        self._sampler.reset(count)
 
 
 def get_rays_np(H, W, K, c2w):
@@ -958,6 +1174,120 @@ class CapturedMultiPoseStep(CapturedPoseStep):
         losses = img2mse_each(rgb.reshape(self.cam_transf.n_poses, self.pixels.shape[0], 3), self.target)
         losses.sum().backward()
         return losses.detach()
+
+
+class CapturedJointStep(_CapturedStep):
+    """CapturedTrainStep with LEARNED camera poses (BARF / iMAP-style mapping: every training image has its own correctable
+    pose), captured once in a HIP graph and replayed:
+
+        [sampler.draw()] -> poses = learned_poses() [M, 4, 4] -> get_rays_indexed(H, W, K, poses, pixels, pose_index)
+        -> render_from_rays -> img2mse(rgb) [+ img2mse(rgb0)] -> loss.backward() -> optimizer.step()
+
+    The fields' training backward returns parameter gradients and ray gradients from one call; the ray gradients go through
+    the indexed ray kernel (one block per pose, fixed order) and the twist kernel to learned_poses.twist.xi.  The optimizer
+    is ONE optim.Adam whose parameter groups hold the field parameters and xi, each with its own learning rate:
+
+        poses = utils.LearnedPoses(noisy_poses, frozen=(0,)).to(device)
+        opt = optim.Adam([{"params": field_params, "lr": lrate}, {"params": [poses.twist.xi], "lr": pose_lr}], betas=(0.9, 0.999))
+        bank = utils.ImageBankSampler(images, N_rand)                                   # [M, H, W, 3] on the device
+        step = utils.CapturedJointStep(renderer, H, W, K, chunk, coarse, fine, poses, opt, N_rand, sampler=bank)
+        for i in range(n_iters):
+            loss = step()                                        # device scalar; step.psnr, step.poses [M, 4, 4] likewise
+            opt.param_groups[0]['lr'] = new_lrate                # read at the next replay, per group
+
+    Without a sampler, step(pixels, pose_index, target) copies pixels [n_rays, 2] = (x, y), pose_index [n_rays] and target
+    [n_rays, 3] into the capture's buffers (host values are checked against the image and [0, M); device tensors are
+    trusted, see get_rays_indexed).  `step.poses` is learned_poses() AFTER the update, `step.loss` / `step.psnr` are as in
+    CapturedTrainStep; all are device tensors that the next replay overwrites.  Same contracts as CapturedTrainStep
+    otherwise: construction leaves parameters, moments, step counts and sampler.draw_count as they were; the renderer is
+    captured as it is (ray bounds, train_occupancy and NDC carry ray gradients).  Refused: an optimizer without xi or with
+    tensors that are neither xi nor a field parameter, and FROZEN fields -- poses against frozen fields are
+    CapturedMultiPoseStep's case (inputs-only backward, no weight-gradient launches)."""
+
+    _ADAM_OVER = "over the field parameters and learned_poses.twist.xi"
+
+    def __init__(self, renderer, H, W, K, chunk, coarse_model, fine_model, learned_poses, optimizer, n_rays, warmup=3, sampler=None):
+        self._take_optimizer(optimizer)
+        if not isinstance(learned_poses, LearnedPoses):
+            raise _lib.NerfAmdError("CapturedJointStep trains a utils.LearnedPoses, got %s" % type(learned_poses).__name__)
+        field = [p for m in (coarse_model, fine_model) if m is not None for p in m.parameters()]
+        if not field or not all(p.requires_grad for p in field):
+            raise _lib.NerfAmdError("CapturedJointStep trains the fields AND the poses; with frozen fields (requires_grad_(False)) "
+                                    "use utils.CapturedMultiPoseStep, whose backward skips the weight gradients")
+        xi = learned_poses.twist.xi
+        held = {id(p) for p in self.params}
+        if id(xi) not in held:
+            raise _lib.NerfAmdError("CapturedJointStep: the optimizer must hold learned_poses.twist.xi (a parameter group of its own, "
+                                    "with the pose learning rate)")
+        if not held <= {id(xi)} | {id(p) for p in field}:
+            raise _lib.NerfAmdError("CapturedJointStep: the optimizer holds tensors that are neither field parameters nor "
+                                    "learned_poses.twist.xi")
+        H, W, n_rays, M = int(H), int(W), int(n_rays), learned_poses.n_poses
+        if sampler is not None:
+            if not isinstance(sampler, ImageBankSampler):
+                raise _lib.NerfAmdError("sampler must be a utils.ImageBankSampler (a PixelSampler draws from ONE image)")
+            if (sampler.M, sampler.H, sampler.W, sampler.n_rays) != (M, H, W, n_rays):
+                raise _lib.NerfAmdError("the sampler draws %d pixels of %d images of %d x %d; this step was asked for %d rays of %d "
+                                        "poses of %d x %d" % (sampler.n_rays, sampler.M, sampler.H, sampler.W, n_rays, M, H, W))
+        _lib.require_device(xi, "learned_poses")
+        dev = xi.device
+        if any(p.device != dev for p in field) or (sampler is not None and sampler.pixels.device != dev):
+            raise _lib.NerfAmdError("CapturedJointStep: fields, poses and sampler must be on one device (%s)" % dev)
+        self.renderer, self.models, self.learned_poses, self.sampler = renderer, (coarse_model, fine_model), learned_poses, sampler
+        self.args = (H, W, K, chunk)
+        if sampler is not None:
+            self.pixels, self.target, self.pose_index = sampler.pixels, sampler.target, None     # stacked rows name the image
+            draws_before = sampler.draw_count.clone()
+        else:
+            # a valid placeholder batch for the warm-up: pixel (0, 0) of image 0 n_rays times, a grey target
+            self.pixels = torch.zeros(n_rays, 2, device=dev, dtype=torch.int32)
+            self.pose_index = torch.zeros(n_rays, device=dev, dtype=torch.int32)
+            self.target = torch.full((n_rays, 3), 0.5, device=dev)
+        self.loss = self.psnr = self.poses = None
+        self.graph = _capture_step(self._body, optimizer, self.params, self.models, dev, warmup)
+        if sampler is not None:
+            sampler.draw_count.copy_(draws_before)                # the warm-up draws do not count
+        with torch.no_grad():
+            self.poses.copy_(learned_poses())                     # (the capture left the poses of its own last update there)
+
+    def _body(self):
+        H, W, K, chunk = self.args
+        coarse, fine = self.models
+        for p in self.params:
+            p.grad = None
+        if self.sampler is not None:
+            self.sampler.draw()                   # fills self.pixels / self.target (the sampler's buffers)
+        poses = self.learned_poses()
+        rays_o, rays_d = get_rays_indexed(H, W, K, poses, self.pixels, self.pose_index)
+        rgb, disp, acc, extras = self.renderer.render_from_rays(H, W, K, chunk, torch.stack([rays_o, rays_d], 0), coarse, fine,
+                                                                retraw=True)
+        loss = img2mse(rgb, self.target)
+        self.psnr = -10. * torch.log(loss.detach()) / math.log(10.)
+        if 'rgb0' in extras:
+            loss = loss + img2mse(extras['rgb0'], self.target)
+        loss.backward()
+        self.optimizer.step()
+        self.loss = loss.detach()
+        with torch.no_grad():
+            self.poses = self.learned_poses()
+
+    def __call__(self, pixels=None, pose_index=None, target=None):
+        H, W = self.args[0], self.args[1]
+        given = [a is not None for a in (pixels, pose_index, target)]
+        if self.sampler is not None:
+            if any(given):
+                raise _lib.NerfAmdError("this step draws its own pixels (sampler=...): call step() without arguments")
+        else:
+            if not all(given):
+                raise _lib.NerfAmdError("step(pixels, pose_index, target): a step built without a sampler needs all three")
+            dev = self.pixels.device
+            pix = pixels if (isinstance(pixels, torch.Tensor) and pixels.is_cuda) else _device_pixels(pixels, H, W, dev)
+            idx = pose_index if (isinstance(pose_index, torch.Tensor) and pose_index.is_cuda) else \
+                _host_pose_index(pose_index, self.pixels.shape[0], self.learned_poses.n_poses)
+            self.pixels.copy_(pix, non_blocking=True)
+            self.pose_index.copy_(idx, non_blocking=True)
+            self.target.copy_(target, non_blocking=True)
+        return self._replay()
 
 
 def multistart_scores(losses, window=10):

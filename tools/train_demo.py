@@ -11,6 +11,11 @@ mse(rgb) + mse(rgb0) -> Adam with exponential lr decay).  Prints PSNR on a held-
 Renderer.ray_bounds), from the moment the grid is filled, and for the test renders.
 --live-sampler P places the coarse samples in each ray's live stretches, probed at P points (occupancy.LiveSampler,
 Renderer.coarse_sampler; --live-sampler-pad widens every stretch), from the same moment and for the test renders.  Off by default.
+
+    python tools/train_demo.py --refine-poses 3 0.1 [--pose-lr 1e-3] [--freeze-views 1] [--steps 2000] [--out FILE]
+
+--refine-poses ROT_DEG TRANS perturbs every training pose and trains the field and the poses jointly (utils.CapturedJointStep over
+utils.LearnedPoses and utils.ImageBankSampler), beside plain training on the perturbed and on the true poses: run_refine_poses.
 """
 import argparse
 import json
@@ -277,8 +282,110 @@ def run(steps=600, res=64, views=12, n_rand=1024, seed=0, verbose=True, scene_di
     return out, (coarse, fine, opt, args, renderer, (H, W, K), poses_t, images, i_test)
 
 
+def rigid_alignment(src, dst):
+    """The rigid motion (R [3, 3], t [3]; no scale) that best maps the points src [n, 3] onto dst [n, 3] (Kabsch)."""
+    cs, cd = src.mean(0), dst.mean(0)
+    U, _, Vt = np.linalg.svd((dst - cd).T @ (src - cs))
+    R = U @ np.diag([1.0, 1.0, np.sign(np.linalg.det(U @ Vt))]) @ Vt
+    return R, cd - R @ cs
+
+
+def pose_errors(est, true):
+    """Rotation (degrees) and translation error of the poses est [n, 4, 4] against true [n, 4, 4], mean over the views, after
+    the rigid alignment of the camera centres (a reconstruction is defined up to a rigid motion); also the 4 x 4 alignment."""
+    est, true = np.asarray(est, np.float64), np.asarray(true, np.float64)
+    R, t = rigid_alignment(est[:, :3, 3], true[:, :3, 3])
+    A = np.eye(4)
+    A[:3, :3], A[:3, 3] = R, t
+    moved = A @ est
+    cosines = [(np.trace(m[:3, :3].T @ q[:3, :3]) - 1.0) / 2.0 for m, q in zip(moved, true)]
+    rot = float(np.degrees(np.arccos(np.clip(cosines, -1.0, 1.0))).mean())
+    return rot, float(np.linalg.norm(moved[:, :3, 3] - true[:, :3, 3], axis=1).mean()), A
+
+
+def run_refine_poses(rot_deg, trans, steps=2000, res=64, views=12, n_rand=1024, seed=0, lrate=5e-4, pose_lr=1e-3, freeze_views=1,
+                     precision="fp32_split", verbose=True):
+    """--refine-poses: three legs on the sphere scene with the same seed and steps,
+      joint            the training poses perturbed (each view by its own rotation of rot_deg about a random axis and a
+                       translation of length trans, utils.perturbed_start_poses' noise), field and poses trained together
+                       (utils.CapturedJointStep + utils.ImageBankSampler; the first freeze_views views keep their given pose);
+      plain_perturbed  the reference's training on the perturbed poses (utils.CapturedTrainStep);
+      plain_true       the same on the true poses.
+    Per leg: rotation / translation error of the training poses before and after (pose_errors), and the PSNR of the held-out
+    view rendered at its true pose carried into the leg's own frame by the inverse alignment.  Results to report, not gates."""
+    from nerf_shared_amd import optim
+    dev = torch.device("cuda:0")
+    H = W = res
+    K = synth.lego_intrinsics(H, W)
+    true = np.stack([np.concatenate([synth.pose_spherical(th, -30.0 + 20.0 * np.sin(i)), [[0, 0, 0, 1]]], 0)
+                     for i, th in enumerate(np.linspace(-180, 180, views + 1)[:-1])], 0).astype(np.float32)
+    images = torch.stack([sphere_image(H, W, K, p[:3, :4], dev) for p in true], 0).contiguous()
+    i_train, i_test = list(range(1, views)), 0
+    noisy = true.copy()
+    for i in i_train:
+        noisy[i] = utils.perturbed_start_poses(true[i], 2, rot_deg, trans, seed=1000 * seed + i)[1]
+    lr_at = lambda i, base: base * (0.1 ** (i / 250000.0))          # noqa: E731  (main.py:108-112)
+    legs = {}
+    for leg in ("joint", "plain_perturbed", "plain_true"):
+        torch.manual_seed(seed)
+        np.random.seed(seed)
+        given = true if leg == "plain_true" else noisy
+        args = SimpleNamespace(N_rand=n_rand, no_batching=False, lrate=lrate, lrate_decay=250, netdepth=8, netwidth=256,
+                               netdepth_fine=8, netwidth_fine=256, N_importance=128, use_viewdirs=True, multires=10,
+                               multires_views=4, i_embed=0)
+        coarse, fine = utils.create_nerf_models(args, dev)
+        coarse.precision = fine.precision = precision
+        renderer = render_utils.Renderer(perturb=1.0, N_importance=128, N_samples=64, use_viewdirs=True, white_bkgd=True,
+                                         raw_noise_std=0.0, near=2.0, far=6.0)
+        field = list(coarse.parameters()) + list(fine.parameters())
+        before = pose_errors(given[i_train], true[i_train])
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        if leg == "joint":
+            learned = utils.LearnedPoses(given[i_train], frozen=range(freeze_views)).to(dev)
+            opt = optim.Adam([{"params": field, "lr": lrate}, {"params": [learned.twist.xi], "lr": pose_lr}], betas=(0.9, 0.999))
+            bank = utils.ImageBankSampler(images[i_train].contiguous(), n_rand, seed=seed)
+            step = utils.CapturedJointStep(renderer, H, W, K, 32768, coarse, fine, learned, opt, n_rand, sampler=bank)
+            for i in range(steps):
+                loss = step()
+                opt.param_groups[0]["lr"], opt.param_groups[1]["lr"] = lr_at(i, lrate), lr_at(i, pose_lr)
+            final = step.poses.detach().cpu().numpy()
+        else:
+            opt = optim.Adam(field, lr=lrate, betas=(0.9, 0.999))
+            _, poses_t, rays_rgb, use_batching, N_rand, i_batch = utils.batch_training_data(args, given, (H, W, K[0][0]), K, images, i_train)
+            step = utils.CapturedTrainStep(renderer, H, W, K, 32768, coarse, fine, opt, n_rand)
+            for i in range(steps):
+                rays, target, rays_rgb, i_batch = utils.sample_random_ray_batch(args, images, poses_t, rays_rgb, N_rand, use_batching,
+                                                                                i_batch, i_train, (H, W, K[0][0]), K, 0, i)
+                loss = step(rays, target)
+                opt.param_groups[0]["lr"] = lr_at(i, lrate)
+            final = given[i_train]
+        torch.cuda.synchronize()
+        dt = time.perf_counter() - t0
+        rot, tr, A = pose_errors(final, true[i_train])
+        test_pose = torch.from_numpy((np.linalg.inv(A) @ true[i_test].astype(np.float64)).astype(np.float32))
+        with torch.no_grad():
+            rgb = renderer.render(H, W, K, coarse, fine, chunk=32768, c2w=test_pose[:3, :4], retraw=False)[0]
+            psnr = float(utils.mse2psnr(utils.img2mse(rgb, images[i_test])))
+        legs[leg] = {"rot_err_deg_before": before[0], "trans_err_before": before[1], "rot_err_deg_after": rot, "trans_err_after": tr,
+                     "test_psnr": psnr, "final_loss": float(loss), "train_s": dt}
+        if verbose:
+            print(leg, json.dumps(legs[leg]))
+        del step, opt, coarse, fine
+    return {"scene": "sphere", "res": res, "views": views, "train_views": len(i_train), "steps": steps, "rays_per_step": n_rand,
+            "seed": seed, "precision": precision, "perturbation": {"rot_deg": rot_deg, "trans": trans}, "lrate": lrate,
+            "pose_lr": pose_lr, "freeze_views": freeze_views, "legs": legs}
+
+
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
+    ap.add_argument("--refine-poses", type=float, nargs=2, default=None, metavar=("ROT_DEG", "TRANS"),
+                    help="perturb every training pose by this rotation and translation and train field and poses jointly; runs the "
+                    "three legs of run_refine_poses and prints their table")
+    ap.add_argument("--pose-lr", type=float, default=1e-3, help="--refine-poses: the learning rate of the pose twists")
+    ap.add_argument("--freeze-views", type=int, default=1, metavar="N", help="--refine-poses: the first N training views keep their pose (gauge)")
+    ap.add_argument("--precision", choices=["bf16", "fp32_split", "fp32"], default="fp32_split", help="--refine-poses: the fields' arithmetic")
+    ap.add_argument("--out", default=None, help="--refine-poses: write the result here as JSON")
     ap.add_argument("--steps", type=int, default=600)
     ap.add_argument("--res", type=int, default=64)
     ap.add_argument("--views", type=int, default=12)
@@ -300,6 +407,14 @@ if __name__ == "__main__":
                     "live stretches, probed at P points (a power of two in 64..4096; 0: off)")
     ap.add_argument("--live-sampler-pad", type=int, default=1, metavar="N", help="probes every live stretch is widened by, either way")
     a = ap.parse_args()
+    if a.refine_poses is not None:
+        result = run_refine_poses(a.refine_poses[0], a.refine_poses[1], steps=a.steps, res=a.res, views=a.views, n_rand=a.n_rand, seed=a.seed,
+                                  lrate=a.lrate, pose_lr=a.pose_lr, freeze_views=a.freeze_views, precision=a.precision, verbose=not a.quiet)
+        print(json.dumps(result, indent=1))
+        if a.out:
+            with open(a.out, "w") as f:
+                f.write(json.dumps(result, indent=1) + "\n")
+        sys.exit(0)
     print(json.dumps(run(a.steps, a.res, a.views, n_rand=a.n_rand, seed=a.seed, scene_dir=a.scene_dir, multires=a.multires,
                          multires_views=a.multires_views, lrate=a.lrate, ss=a.ss, verbose=not a.quiet, occupancy_res=a.occupancy or None,
                          occupancy_warmup=a.occupancy_warmup, occupancy_refresh=a.occupancy_refresh,
